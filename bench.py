@@ -2,6 +2,21 @@
 """Benchmark of the LSSP Krylov hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 216|256|512]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets the
+system up, runs W warm-up iterations, times K iterations, writes the outputs
+when --dump-outputs is given and prints the result line.  --full adds every
+other leg described below (the SpMV and ILU-apply rooflines and the measured
+HBM peaks before the timed steps; config4 and cpu_baseline after them) to the
+same line.
+--dump-outputs DIR writes what the last timed solve handed back in its last
+step as float64 .npy files: x.npy, the solution vector (x_rank<r>.npy, the rank's
+rows, with N > 1), and residual.npy, the residual norm it returned.  A vector
+of more than DUMP_MAX_ELEMS / N entries is written as a fixed sample of that
+many entries (sorted indices drawn by numpy's default_rng(0)), so one run
+writes under 64 MB.  The inputs depend on the arguments alone, so two builds
+run with the same arguments can be compared file for file.
 
 --gpus N > 1 run directly starts N ranks (torch.distributed.run, one process
 per GPU, 127.0.0.1 rendezvous); under an external launcher WORLD_SIZE must
@@ -11,13 +26,16 @@ Workload: 7-point Poisson on a 216^3 grid (n = 10,077,696 rows, 70,263,936
 nnz -- the "n=10M" of BASELINE.json), fp64, b = 1, x0 = 0, BiCGSTAB with an
 ILUK(0) preconditioner (solver-bicgstab.cxx, pc-iluk.cxx).  One STEP is one
 BiCGSTAB iteration: 2 SpMV, 2 ILU applies (4 triangular sweeps), 4 dots and
-2 norms.  The solve runs with zero tolerances, so it performs exactly the
-requested number of iterations.  value = iterations per second of the whole
-job.  With N > 1 (torchrun, one process per GPU) the same global matrix is
-row-partitioned into N z-slabs (strong scaling); halos move with RCCL
+2 norms.  A solve runs with zero tolerances, so it performs exactly the
+requested number of iterations; the K steps are solves of at most
+--solve-iters (100) iterations, each from x0 = 0, because one solve run on
+converges and then ends early where the reference's driver does (||s|| = 0).
+value = iterations per second of the whole job.  With N > 1 (torchrun, one
+process per GPU) the same global matrix is row-partitioned into N z-slabs (strong scaling); halos move with RCCL
 send/recv and dots with an RCCL all-gather; the preconditioner becomes
 block-Jacobi ILU(0) per slab (the reference's blk_size path).
 
+The legs of --full:
 The roofline object describes the dominant operator, the ILU(0) apply
 (pc.solve: the rhs gather and the two line sweeps k_line2, L then U --
 rocprof attributes ~65% of a step to them); roofline_spmv describes the
@@ -48,6 +66,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_MAX_ELEMS = 6_000_000  # --dump-outputs: fp64 entries per run (48 MB), shared by the ranks
 
 
 def spmv_bytes(nnz: int, n: int, coded: bool = False) -> int:
@@ -176,6 +195,83 @@ def measure_hbm_peak(dev, stream, gpu, e0, e1):
         return None, {"error": repr(ex)[:200]}
 
 
+def roofline_legs(dev, A, M, nl: int, nnz_local: int, rank: int, gpu: int, args):
+    """--full: the SpMV and ILU-apply roofline legs and (rank 0) the measured HBM
+    peaks, timed with HIP events on the library's stream; returns the figures
+    the result line's spmv / roofline / roofline_spmv objects are built from."""
+    import torch
+
+    y = dev.vec(A.nx)
+    # ---- SpMV roofline leg: y = A x, HIP events on the library's stream ----
+    xs = dev.vec(A.nx, np.random.default_rng(rank).uniform(-1, 1, A.nx))
+    stream = torch.cuda.ExternalStream(dev.stream)
+    for _ in range(5):
+        A.mv_mxy(xs, y)
+    dev.sync()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for _ in range(args.spmv_reps):
+        A.mv_mxy(xs, y)
+    e1.record(stream)
+    e1.synchronize()
+    spmv_ms = e0.elapsed_time(e1) / args.spmv_reps
+    ndiag = A.ndiag
+    spmv_b = spmv_bytes(nnz_local, nl, coded=ndiag > 0)
+    spmv_gbs = spmv_b / (spmv_ms * 1e-3) / 1e9
+    csr_equiv_gbs = spmv_bytes(nnz_local, nl) / (spmv_ms * 1e-3) / 1e9
+
+    # ---- ILU apply roofline leg (the dominant operator): applies enqueued back
+    # to back (lssp_amd_ilu_apply_async; the synchronous C-ABI apply adds a host
+    # round trip per call that a solve's queued applies do not pay) ----
+    zs = dev.vec(A.nx)
+    for _ in range(3):
+        M.apply(zs, xs)
+    e0.record(stream)
+    for _ in range(args.apply_reps):
+        M.apply_async(zs, xs)
+    e1.record(stream)
+    e1.synchronize()
+    M.check()
+    apply_ms = e0.elapsed_time(e1) / args.apply_reps
+    apply_b = ilu_apply_bytes(M.nnzL, M.nnzU, nl)
+    apply_gbs = apply_b / (apply_ms * 1e-3) / 1e9
+
+    # ---- measured HBM copy / read peak (rank 0) ----
+    peak_measured, peak_detail = None, None
+    if rank == 0:
+        peak_measured, peak_detail = measure_hbm_peak(dev, stream, gpu, e0, e1)
+    return {"vecs": (y, xs, zs), "ndiag": ndiag, "spmv_ms": spmv_ms, "spmv_b": spmv_b, "spmv_gbs": spmv_gbs,
+            "csr_equiv_gbs": csr_equiv_gbs, "apply_ms": apply_ms, "apply_b": apply_b, "apply_gbs": apply_gbs,
+            "peak_measured": peak_measured, "peak_detail": peak_detail}
+
+
+def full_objects(legs, M, spmv_gbs_total: float):
+    """--full: the result line's spmv, roofline and roofline_spmv objects"""
+    ndiag, peak_measured = legs["ndiag"], legs["peak_measured"]
+    spmv_ms, spmv_b, spmv_gbs = legs["spmv_ms"], legs["spmv_b"], legs["spmv_gbs"]
+    apply_ms, apply_b, apply_gbs = legs["apply_ms"], legs["apply_b"], legs["apply_gbs"]
+    return {
+        "spmv": {"gbps": round(spmv_gbs_total, 1), "frac_hbm_peak": round(spmv_gbs / HBM_PEAK_GBS, 4),
+                 "ms_per_call": round(spmv_ms, 5),
+                 "column_stream": (f"1-byte diagonal ids ({ndiag} offsets)" if ndiag else "int32 columns"),
+                 "csr_int32_equivalent_gbps": round(legs["csr_equiv_gbs"], 1)},
+        "roofline": {"bound": "hbm", "achieved": round(apply_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(apply_gbs / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("ilu_apply"),
+                     "kernel": "ILU(0) apply = k_line_rhs (rhs -> the L sweep's stream) + k_line2 (L sweep "
+                               "-> the U sweep's rhs stream) + k_line2 (U sweep -> x in natural order); "
+                               f"latency-bound: 2 x {M.levelsL} dependent levels, two per workgroup step",
+                     "bytes_per_launch": apply_b, "ms_per_launch": round(apply_ms, 5),
+                     "peak_measured": peak_measured, "peak_measured_detail": legs["peak_detail"],
+                     "frac_of_measured_peak": round(apply_gbs / peak_measured, 4) if peak_measured else None},
+        "roofline_spmv": {"bound": "hbm", "achieved": round(spmv_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(spmv_gbs / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("k_spmv3"),
+                          "kernel": f"k_spmv3<EPI_MXY,0,{'true' if ndiag else 'false'}> (y = A x)",
+                          "bytes_per_launch": spmv_b, "ms_per_launch": round(spmv_ms, 5),
+                          "peak_measured": peak_measured,
+                          "frac_of_measured_peak": round(spmv_gbs / peak_measured, 4) if peak_measured else None},
+    }
+
+
 def config4_leg(dev, rank: int, world: int, steps: int, warmup: int = 2):
     """Config 4 (BASELINE.json configs[3]): 7-pt Poisson 512^3 (n = 134,217,728),
     BiCGSTAB + ILU(0), row-partitioned over the same N ranks as the headline
@@ -237,6 +333,20 @@ def config4_leg(dev, rank: int, world: int, steps: int, warmup: int = 2):
     return out
 
 
+def dump_outputs(path: str, x, nl: int, res, rank: int, world: int):
+    """--dump-outputs: the timed solve's solution (the rank's nl rows; a fixed
+    sample of them when they exceed the rank's share of DUMP_MAX_ELEMS) and the
+    residual norm it returned, as float64 .npy files"""
+    os.makedirs(path, exist_ok=True)
+    xh = x.download(nl)
+    cap = DUMP_MAX_ELEMS // world
+    if nl > cap:
+        xh = xh[np.sort(np.random.default_rng(0).choice(nl, cap, replace=False))]
+    np.save(os.path.join(path, "x.npy" if world == 1 else f"x_rank{rank}.npy"), xh)
+    if rank == 0:
+        np.save(os.path.join(path, "residual.npy"), np.array([res.residual], dtype=np.float64))
+
+
 def free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -262,6 +372,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--grid", type=int, default=216)
+    ap.add_argument("--solve-iters", type=int, default=100,
+                    help="the steps run as solves of at most this many iterations, each from x0 = 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed solve's outputs to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the SpMV / ILU-apply roofline legs, the measured HBM peaks, config 4 and the "
+                         "CPU baseline (the options below steer these legs)")
     ap.add_argument("--spmv-reps", type=int, default=50)
     ap.add_argument("--apply-reps", type=int, default=10)
     ap.add_argument("--cpu-iters", type=int, default=8)
@@ -275,6 +392,10 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.solve_iters < 1:
+        ap.error("--solve-iters must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: start the N ranks under torch.distributed.run as a
         # child (nothing has touched the GPU in this process) and exit with its code
@@ -314,56 +435,32 @@ def main():
     nnz_local = int(Ap[-1])
     x = dev.vec(A.nx, np.zeros(A.nx))
     b = dev.vec(A.nx, np.ones(A.nx))
-    y = dev.vec(A.nx)
     t_setup = time.perf_counter() - t_setup0
 
     comm_ranks = dev.comm_nranks() if world > 1 else 1
     if comm_ranks != world:
         raise SystemExit(f"bench.py: the communicator has {comm_ranks} ranks, WORLD_SIZE={world}")
 
-    # ---- SpMV roofline leg: y = A x, HIP events on the library's stream ----
-    xs = dev.vec(A.nx, np.random.default_rng(rank).uniform(-1, 1, A.nx))
-    stream = torch.cuda.ExternalStream(dev.stream)
-    for _ in range(5):
-        A.mv_mxy(xs, y)
-    dev.sync()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(args.spmv_reps):
-        A.mv_mxy(xs, y)
-    e1.record(stream)
-    e1.synchronize()
-    spmv_ms = e0.elapsed_time(e1) / args.spmv_reps
-    ndiag = A.ndiag
-    spmv_b = spmv_bytes(nnz_local, nl, coded=ndiag > 0)
-    spmv_gbs = spmv_b / (spmv_ms * 1e-3) / 1e9
-    csr_equiv_gbs = spmv_bytes(nnz_local, nl) / (spmv_ms * 1e-3) / 1e9
-
-    # ---- ILU apply roofline leg (the dominant operator): applies enqueued back
-    # to back (lssp_amd_ilu_apply_async; the synchronous C-ABI apply adds a host
-    # round trip per call that a solve's queued applies do not pay) ----
-    zs = dev.vec(A.nx)
-    for _ in range(3):
-        M.apply(zs, xs)
-    e0.record(stream)
-    for _ in range(args.apply_reps):
-        M.apply_async(zs, xs)
-    e1.record(stream)
-    e1.synchronize()
-    M.check()
-    apply_ms = e0.elapsed_time(e1) / args.apply_reps
-    apply_b = ilu_apply_bytes(M.nnzL, M.nnzU, nl)
-    apply_gbs = apply_b / (apply_ms * 1e-3) / 1e9
-
-    # ---- measured HBM copy / read peak (rank 0) ----
-    peak_measured, peak_detail = None, None
-    if rank == 0:
-        peak_measured, peak_detail = measure_hbm_peak(dev, stream, gpu, e0, e1)
+    # ---- --full: the roofline legs and the measured HBM peaks, before the steps ----
+    legs = roofline_legs(dev, A, M, nl, nnz_local, rank, gpu, args) if args.full else None
 
     # ---- BiCGSTAB steps ----
+    # iters iterations as solves of at most --solve-iters iterations, each from
+    # x0 = 0 (x is zeroed on the device, in the library's stream): one solve run
+    # on converges, and BiCGSTAB then ends early on ||s|| = 0 as the reference's
+    # driver does (near 800 iterations on 216^3), so a long run repeats the
+    # solve's unconverged start instead.  Returns the last solve's result.
     def run(iters):
-        return lssp_amd.solve(dev, A, M, x, b, solver=lssp_amd.BICGSTAB, tol_rel=0.0, tol_abs=0.0, tol_rb=0.0,
-                              maxit=iters)
+        done = 0
+        while done < iters:
+            k = min(args.solve_iters, iters - done)
+            st = dev.L.lssp_amd_vec_set_value(dev.h, x.ptr, A.nx, 0.0)
+            assert st == 0, st
+            res = lssp_amd.solve(dev, A, M, x, b, solver=lssp_amd.BICGSTAB, tol_rel=0.0, tol_abs=0.0, tol_rb=0.0,
+                                 maxit=k)
+            assert res.nits == k, f"expected {k} iterations in one solve, got {res.nits}"
+            done += k
+        return res
 
     if args.warmup > 0:
         run(args.warmup)
@@ -382,12 +479,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        g = torch.tensor([spmv_gbs], dtype=torch.float64)
-        dist.all_reduce(g, op=dist.ReduceOp.SUM)
-        spmv_gbs_total = float(g.item())
-    else:
-        spmv_gbs_total = spmv_gbs
-    assert res.nits == args.steps, f"expected {args.steps} iterations, got {res.nits}"
+    spmv_gbs_total = None
+    if legs is not None:
+        spmv_gbs_total = legs["spmv_gbs"]
+        if world > 1:
+            g = torch.tensor([spmv_gbs_total], dtype=torch.float64)
+            dist.all_reduce(g, op=dist.ReduceOp.SUM)
+            spmv_gbs_total = float(g.item())
 
     if rank == 0:
         it_s = args.steps / elapsed
@@ -411,38 +509,24 @@ def main():
                        "transport": ("host-staged gloo, all ranks on GPU 0 (rehearsal, not a scaling number)"
                                      if args.share_gpu and world > 1 else "rccl" if world > 1 else "none"),
                        "comm_ranks": comm_ranks},
-            "spmv": {"gbps": round(spmv_gbs_total, 1), "frac_hbm_peak": round(spmv_gbs / HBM_PEAK_GBS, 4),
-                     "ms_per_call": round(spmv_ms, 5),
-                     "column_stream": (f"1-byte diagonal ids ({ndiag} offsets)" if ndiag else "int32 columns"),
-                     "csr_int32_equivalent_gbps": round(csr_equiv_gbs, 1)},
-            "roofline": {"bound": "hbm", "achieved": round(apply_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(apply_gbs / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("ilu_apply"),
-                         "kernel": "ILU(0) apply = k_line_rhs (rhs -> the L sweep's stream) + k_line2 (L sweep "
-                                   "-> the U sweep's rhs stream) + k_line2 (U sweep -> x in natural order); "
-                                   f"latency-bound: 2 x {M.levelsL} dependent levels, two per workgroup step",
-                         "bytes_per_launch": apply_b, "ms_per_launch": round(apply_ms, 5),
-                         "peak_measured": peak_measured, "peak_measured_detail": peak_detail,
-                         "frac_of_measured_peak": round(apply_gbs / peak_measured, 4) if peak_measured else None},
-            "roofline_spmv": {"bound": "hbm", "achieved": round(spmv_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": round(spmv_gbs / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("k_spmv3"),
-                              "kernel": f"k_spmv3<EPI_MXY,0,{'true' if ndiag else 'false'}> (y = A x)",
-                              "bytes_per_launch": spmv_b, "ms_per_launch": round(spmv_ms, 5),
-                              "peak_measured": peak_measured,
-                              "frac_of_measured_peak": round(spmv_gbs / peak_measured, 4) if peak_measured else None},
             "ilu": {"levels_L": M.levelsL, "levels_U": M.levelsU, "setup_s": round(M.setup_seconds, 3)},
             "setup_s": round(t_setup, 2),
         }
-    # ---- config 4 (512^3 over the same ranks): the scaling curve's matrix ----
-    if N == 512:
-        args.config4_steps = 0  # the headline is config 4's matrix already
+        if legs is not None:
+            out.update(full_objects(legs, M, spmv_gbs_total))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, nl, res, rank, world)
+    # ---- --full: config 4 (512^3 over the same ranks): the scaling curve's matrix ----
+    if N == 512 or not args.full:
+        args.config4_steps = 0  # the headline is config 4's matrix already / a plain run
     if args.config4_steps > 0:
-        for o in (x, b, y, xs, zs, M, A):
+        for o in (x, b, *legs["vecs"], M, A):
             o.close()
         c4 = config4_leg(dev, rank, world, args.config4_steps)
     if rank == 0:
         if args.config4_steps > 0:
             out["config4"] = c4
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(N, args.cpu_iters)
         print(json.dumps(out), flush=True)
     dev.close()

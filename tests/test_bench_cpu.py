@@ -3,6 +3,7 @@ import importlib.util
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,3 +45,41 @@ def test_world_size_must_match_gpus(monkeypatch):
     with pytest.raises(SystemExit) as e:
         b.main()
     assert "WORLD_SIZE=2" in str(e.value.code)
+
+
+class _Vec:
+    def __init__(self, a):
+        self.a = a
+
+    def download(self, n=None):
+        return self.a[:n].copy()
+
+
+class _Res:
+    residual = 0.125
+
+
+def test_dump_outputs_small_vector_whole(tmp_path):
+    b = _bench()
+    a = np.arange(12, dtype=np.float64)
+    b.dump_outputs(str(tmp_path / "d"), _Vec(a), 10, _Res(), 0, 1)
+    assert sorted(os.listdir(tmp_path / "d")) == ["residual.npy", "x.npy"]
+    x = np.load(tmp_path / "d" / "x.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, a[:10])  # the rank's rows, not the halo
+    assert np.array_equal(np.load(tmp_path / "d" / "residual.npy"), [0.125])
+
+
+def test_dump_outputs_large_vector_fixed_sample(tmp_path, monkeypatch):
+    """a vector above the cap is written as the same sorted sample every time,
+    and the ranks share the cap: one run stays under 64 MB"""
+    b = _bench()
+    assert 8 * b.DUMP_MAX_ELEMS + 8 <= 64e6
+    monkeypatch.setattr(b, "DUMP_MAX_ELEMS", 100)
+    a = np.random.default_rng(1).uniform(-1, 1, 1000)
+    for d in ("d1", "d2"):
+        b.dump_outputs(str(tmp_path / d), _Vec(a), 1000, _Res(), 1, 2)
+    x1, x2 = np.load(tmp_path / "d1" / "x_rank1.npy"), np.load(tmp_path / "d2" / "x_rank1.npy")
+    assert x1.shape == (50,) and np.array_equal(x1, x2)
+    idx = np.flatnonzero(np.isin(a, x1))
+    assert idx.size == 50 and np.array_equal(a[idx], x1)  # distinct entries, in row order
+    assert os.listdir(tmp_path / "d1") == ["x_rank1.npy"]  # the residual is rank 0's to write

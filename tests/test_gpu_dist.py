@@ -407,7 +407,7 @@ def test_bench_gpus_2_launches_two_ranks():
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--grid", "32",
                         "--steps", "5", "--warmup", "1", "--no-cpu", "--spmv-reps", "3", "--apply-reps", "2",
-                        "--config4-steps", "0"],
+                        "--config4-steps", "0", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

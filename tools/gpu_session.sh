@@ -7,8 +7,8 @@
 # Every step runs under its own time limit; the first failing step ends the
 # session (no further GPU work after a fault, abort or timeout).  Outputs go
 # to gpurun_out/OUT/.  Steps:
-#   bench            python bench.py (headline + config4 + cpu_baseline) -> bench.json
-#   prof             rocprofv3 --kernel-trace --stats of bench.py --steps 30 -> prof_bench/
+#   bench            python bench.py --full (headline + rooflines + config4 + cpu_baseline) -> bench.json
+#   prof             rocprofv3 --kernel-trace --stats of bench.py --full --steps 30 -> prof_bench/
 #   pmc              two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) -> pmc_traffic.json
 #   tests[=EXPR]     pytest -m gpu (optionally -k EXPR) -> pytest.log
 #   file=PATH        pytest -m gpu on one test file -> pytest_<name>.log
@@ -33,16 +33,16 @@ for step in "$@"; do
   echo "== $step ($(date +%T))"
   case "$step" in
   bench)
-    timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; fail $step $?; }
+    timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; fail $step $?; }
     python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['roofline']['ms_per_launch'], d['roofline']['frac'], d['roofline_spmv']['frac'], (d.get('config4') or {}).get('value'), (d.get('cpu_baseline') or {}).get('value'))"
     ;;
   prof)
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --steps 30 --no-cpu --config4-steps 0 > $O/prof_bench.log 2>&1 || { tail -20 $O/prof_bench.log; fail $step $?; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --full --steps 30 --no-cpu --config4-steps 0 > $O/prof_bench.log 2>&1 || { tail -20 $O/prof_bench.log; fail $step $?; }
     find $O/prof_bench -name "*kernel_stats.csv"
     ;;
   pmc)
-    timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o fetch -- python3 bench.py --steps 10 --warmup 2 --no-cpu --config4-steps 0 > $O/pmc_fetch.log 2>&1 || { tail -5 $O/pmc_fetch.log; fail $step $?; }
-    timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o write -- python3 bench.py --steps 10 --warmup 2 --no-cpu --config4-steps 0 > $O/pmc_write.log 2>&1 || { tail -5 $O/pmc_write.log; fail $step $?; }
+    timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o fetch -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu --config4-steps 0 > $O/pmc_fetch.log 2>&1 || { tail -5 $O/pmc_fetch.log; fail $step $?; }
+    timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o write -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu --config4-steps 0 > $O/pmc_write.log 2>&1 || { tail -5 $O/pmc_write.log; fail $step $?; }
     python3 tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write $O/pmc_traffic.json || fail $step $?
     ;;
   tests|tests=*)

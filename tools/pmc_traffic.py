@@ -1,4 +1,4 @@
-"""Reduce rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of bench.py to HBM bytes
+"""Reduce rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE runs of bench.py --full to HBM bytes
 per launch (tuning aid; writes profiles/pmc_traffic.json read by bench.py).
 
     python tools/pmc_traffic.py <FETCH run dir> <WRITE run dir> [out.json]
