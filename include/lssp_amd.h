@@ -38,14 +38,14 @@ enum {
 
 /* LSSP_SOLVER_TYPE values of the reference (type-defs.h:157-178) */
 enum {
-    LSSP_AMD_GMRES = 0, LSSP_AMD_LGMRES = 1, LSSP_AMD_RGMRES = 2, LSSP_AMD_BICGSTAB = 4,
+    LSSP_AMD_GMRES = 0, LSSP_AMD_LGMRES = 1, LSSP_AMD_RGMRES = 2, LSSP_AMD_RLGMRES = 3, LSSP_AMD_BICGSTAB = 4,
     LSSP_AMD_BICGSAFE = 6, LSSP_AMD_CG = 7, LSSP_AMD_CGS = 8, LSSP_AMD_GPBICG = 9, LSSP_AMD_CR = 10,
     LSSP_AMD_CRS = 11, LSSP_AMD_BICRSTAB = 12, LSSP_AMD_BICRSAFE = 13, LSSP_AMD_GPBICR = 14,
     LSSP_AMD_QMRCGSTAB = 15, LSSP_AMD_TFQMR = 16, LSSP_AMD_ORTHOMIN = 17,
     LSSP_AMD_BICGSTABL = 5, LSSP_AMD_IDRS = 18
 };
 /* ILU kinds (LSSP_PC_TYPE, type-defs.h:63-101) */
-enum { LSSP_AMD_ILUK = 1, LSSP_AMD_ILUT = 2 };
+enum { LSSP_AMD_ILUK = 1, LSSP_AMD_ILUT = 2, LSSP_AMD_BILUK = 3 };
 
 typedef struct lssp_amd_ctx lssp_amd_ctx; /* one device + stream + scratch */
 typedef struct lssp_amd_mat lssp_amd_mat; /* device CSR (lssp_mat_csr, type-defs.h:15-24) */
@@ -178,6 +178,36 @@ int lssp_amd_ilu_get_factors(const lssp_amd_ilu *M, int *Lp, int *Lj, double *Lx
  * (*lines = 16 lines of j + k, *planes = 8); 0 (and 0 x 0) for the general
  * packet sweeps.  Any pointer may be NULL. */
 int lssp_amd_ilu_sweep_layout(const lssp_amd_ilu *M, int *line, int *lines, int *planes);
+
+/* ---- BILUK: block ILU(level) on bs x bs blocks (lssp_pc_biluk_assemble,
+ *      pc-biluk.cxx:388-431; the reference passes num_blks = n / bs).  The apply
+ *      is y = L^-1 rhs, z = D y, x = U^-1 z (lssp_pc_bilu_solve, :22-60), D the
+ *      inverted diagonal blocks.  The reference's block values depend on its
+ *      BLAS / LAPACK; this library fixes one arithmetic of its own (DESIGN.md
+ *      3.7), the same bits on the host and the device path.  A handle works with
+ *      lssp_amd_ilu_apply / _apply_async / _check / _trisolve / _info /
+ *      _get_factors / _destroy and lssp_amd_solve like any other.  Single rank
+ *      only (no block-Jacobi blk argument).
+ * n % bs == 0 and 1 <= bs <= 32, else EINVAL.  level < 0: default 1.  bs <= 8
+ * runs the numeric factorization on the GPU, larger blocks on the host.  A
+ * block row without a diagonal block gets the identity as its inverse; an
+ * exactly singular diagonal block returns LSSP_AMD_EINVAL (the reference
+ * exits). */
+int lssp_amd_bilu_create(lssp_amd_ctx *ctx, int n, const int *Ap, const int *Aj, const double *Ax,
+                         int level, int bs, lssp_amd_ilu **M);
+/* caller-made factors (what the reference's host setup leaves in pc.L / pc.D / pc.U):
+ * L unit diagonal LAST, U unit diagonal FIRST, D block diagonal CSR */
+int lssp_amd_ilu_from_ldu(lssp_amd_ctx *ctx, int n, const int *Lp, const int *Lj, const double *Lx,
+                          const int *Dp, const int *Dj, const double *Dx,
+                          const int *Up, const int *Uj, const double *Ux, lssp_amd_ilu **M);
+/* *bs = 0 for an ILUK/ILUT handle; else Dinv (may be NULL) receives n*bs doubles,
+ * block i column-major at Dinv + i*bs*bs */
+int lssp_amd_ilu_get_diag(const lssp_amd_ilu *M, int *bs, double *Dinv);
+/* HOST ONLY (no context, runs without a GPU): the same factors by the host path.
+ * Two calls like lssp_amd_csr_to_bcsr: with Lj == NULL only *nnzL / *nnzU are set. */
+int lssp_amd_bilu_factor_host(int n, const int *Ap, const int *Aj, const double *Ax, int level, int bs,
+                              int *nnzL, int *nnzU, int *Lp, int *Lj, double *Lx, double *Dinv,
+                              int *Up, int *Uj, double *Ux);
 
 /* ---- Krylov solve: lssp_solver_solve (lssp.cxx:250-414) for BiCGSTAB
  *      (solver-bicgstab.cxx:10-175), GMRES(m) (solver-gmres.cxx:12-255),

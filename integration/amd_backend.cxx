@@ -1,7 +1,8 @@
 // amd_backend.cxx -- the reference-side binding: route LSSP's Krylov hot path
-// (all 18 internal Krylov drivers: BiCGSTAB, BiCGSTAB(l), GMRES(m), GMRES-R(m),
-// LGMRES(m, k), CG, CGS, CR, CRS, BiCGSafe, BiCRSTAB, BiCRSafe, GPBiCG, GPBiCR,
-// QMRCGSTAB, TFQMR, ORTHOMIN, IDR(s), with PC_NON, ILUK, ILUT or a user PC whose
+// (all 19 internal Krylov drivers: BiCGSTAB, BiCGSTAB(l), GMRES(m), GMRES-R(m),
+// LGMRES(m, k), LGMRES-R(m, k), CG, CGS, CR, CRS, BiCGSafe, BiCRSTAB, BiCRSafe,
+// GPBiCG, GPBiCR, QMRCGSTAB, TFQMR, ORTHOMIN, IDR(s), with PC_NON, ILUK, ILUT,
+// BILUK (where the reference is built with BLAS and LAPACK) or a user PC whose
 // pc.solve is the ILU apply) and the pc.solve seam itself (lssp_pc_ilu_solve,
 // solver-tri.cxx:57-60) to lssp_amd on MI355X.
 //
@@ -83,7 +84,20 @@ static bool amd_is_ilu(const LSSP_PC &pc)
            (pc.type == LSSP_PC_USER && pc.solve == AMD_CAT(__wrap_, SYM_PC_ILU_SOLVE));
 }
 
-static bool amd_handles(const LSSP_PC &pc) { return pc.type == LSSP_PC_NON || amd_is_ilu(pc); }
+// BILUK exists in the reference only when it is configured with BLAS and LAPACK
+// (type-defs.h:70-74); its factors pc.L / pc.D / pc.U are uploaded as they are
+static bool amd_is_bilu(const LSSP_PC &pc)
+{
+#if USE_BLAS
+#if USE_LAPACK
+    return pc.type == LSSP_PC_BILUK;
+#endif
+#endif
+    (void)pc;
+    return false;
+}
+
+static bool amd_handles(const LSSP_PC &pc) { return pc.type == LSSP_PC_NON || amd_is_ilu(pc) || amd_is_bilu(pc); }
 
 // ---- device state per solver ------------------------------------------------
 struct AmdState {
@@ -92,6 +106,7 @@ struct AmdState {
     int n = 0, nnz = 0;
     lssp_amd_mat *A = NULL;
     const double *Lx = NULL, *Ux = NULL;  // identity of the uploaded factors (pc.L, pc.U)
+    const double *Dx = NULL;              // ... and of a BILUK's pc.D
     lssp_amd_ilu *M = NULL;
     double *x = NULL, *b = NULL;
 };
@@ -101,7 +116,7 @@ static void amd_drop_factors(AmdState &d)
 {
     if (d.M) lssp_amd_ilu_destroy(d.M);
     d.M = NULL;
-    d.Lx = d.Ux = NULL;
+    d.Lx = d.Ux = d.Dx = NULL;
 }
 
 static void amd_drop(const LSSP_SOLVER *s)
@@ -141,9 +156,15 @@ static int amd_solve(LSSP_SOLVER &s, LSSP_PC &pc, int solver)
     }
     if (pc.type == LSSP_PC_NON) {
         amd_drop_factors(d);
-    } else if (!d.M || d.Lx != pc.L.Ax || d.Ux != pc.U.Ax) {
+    } else if (!d.M || d.Lx != pc.L.Ax || d.Ux != pc.U.Ax || (amd_is_bilu(pc) && d.Dx != pc.D.Ax)) {
         amd_drop_factors(d);
-        AMD_CK(lssp_amd_ilu_from_factors(c, n, pc.L.Ap, pc.L.Aj, pc.L.Ax, pc.U.Ap, pc.U.Aj, pc.U.Ax, &d.M));
+        if (amd_is_bilu(pc)) {
+            AMD_CK(lssp_amd_ilu_from_ldu(c, n, pc.L.Ap, pc.L.Aj, pc.L.Ax, pc.D.Ap, pc.D.Aj, pc.D.Ax, pc.U.Ap, pc.U.Aj,
+                                         pc.U.Ax, &d.M));
+            d.Dx = pc.D.Ax;
+        } else {
+            AMD_CK(lssp_amd_ilu_from_factors(c, n, pc.L.Ap, pc.L.Aj, pc.L.Ax, pc.U.Ap, pc.U.Aj, pc.U.Ax, &d.M));
+        }
         d.Lx = pc.L.Ax;
         d.Ux = pc.U.Ax;
     }
@@ -258,9 +279,9 @@ extern "C" void AMD_CAT(__wrap_, SYM_PC_ASSEMBLE)(LSSP_PC &pc, LSSP_SOLVER s)
 }
 
 // One wrapper per driver: the linker's --wrap=SYM sends every call of SYM here
-// and names the original __real_SYM; PCs this library does not hold (BILUK,
-// ITSOL, AMG, user PCs with their own solve) fall through to the reference's
-// own driver.
+// and names the original __real_SYM; PCs this library does not hold (ITSOL,
+// AMG, user PCs with their own solve; BILUK in a build without BLAS / LAPACK
+// does not exist) fall through to the reference's own driver.
 #define AMD_DRIVER(SYM, KIND)                                                   \
     extern "C" int __real_##SYM(LSSP_SOLVER &, LSSP_PC &);                      \
     extern "C" int __wrap_##SYM(LSSP_SOLVER &s, LSSP_PC &pc)                    \
@@ -273,6 +294,11 @@ extern "C" void AMD_CAT(__wrap_, SYM_PC_ASSEMBLE)(LSSP_PC &pc, LSSP_SOLVER s)
 AMD_DRIVER(_Z17lssp_solver_gmresR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_GMRES)
 AMD_DRIVER(_Z18lssp_solver_lgmresR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_LGMRES)
 AMD_DRIVER(_Z19lssp_solver_gmres_rR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_RGMRES)
+// add -Wl,--wrap=_Z20lssp_solver_lgmres_rR12LSSP_SOLVER_R8LSSP_PC_ to the link and define
+// LSSP_AMD_WRAP_LGMRES_R: without the --wrap, __real_ of it would not resolve
+#ifdef LSSP_AMD_WRAP_LGMRES_R
+AMD_DRIVER(_Z20lssp_solver_lgmres_rR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_RLGMRES)
+#endif
 AMD_DRIVER(_Z20lssp_solver_bicgstabR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_BICGSTAB)
 AMD_DRIVER(_Z21lssp_solver_bicgstablR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_BICGSTABL)
 AMD_DRIVER(_Z20lssp_solver_bicgsafeR12LSSP_SOLVER_R8LSSP_PC_, LSSP_AMD_BICGSAFE)

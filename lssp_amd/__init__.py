@@ -19,9 +19,9 @@ _lib.load()
 from .device import (BICGSTAB, CG, GMRES, LGMRES, RGMRES, ILUK, ILUT, SERIAL, TREE, DILU, DMat,  # noqa: E402,F401
                      Device, DIdx, DVec, LsspError, comm_unique_id, poisson, solve, sort_columns,
                      BICGSAFE, CGS, GPBICG, CR, CRS, BICRSTAB, BICRSAFE, GPBICR, QMRCGSTAB, TFQMR, ORTHOMIN,
-                     BICGSTABL, IDRS)
+                     BICGSTABL, IDRS, RLGMRES, BILUK, bilu_factor_host)
 
 __all__ = ["Device", "DIdx", "DVec", "DMat", "DILU", "solve", "poisson", "sort_columns", "LsspError",
            "comm_unique_id", "GMRES", "LGMRES", "RGMRES", "BICGSTAB", "CG", "ILUK", "ILUT", "SERIAL", "TREE",
            "BICGSAFE", "CGS", "GPBICG", "CR", "CRS", "BICRSTAB", "BICRSAFE", "GPBICR", "QMRCGSTAB", "TFQMR", "ORTHOMIN",
-           "BICGSTABL", "IDRS"]
+           "BICGSTABL", "IDRS", "RLGMRES", "BILUK", "bilu_factor_host"]

@@ -69,6 +69,10 @@ SIGNATURES = {
     "lssp_amd_vec_norm": (_ci, [_vp, _vp, _cl, _vp]),
     "lssp_amd_ilu_create": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _cd, _ci, _ci, _pvp]),
     "lssp_amd_ilu_from_factors": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _pvp]),
+    "lssp_amd_bilu_create": (_ci, [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _pvp]),
+    "lssp_amd_ilu_from_ldu": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pvp]),
+    "lssp_amd_ilu_get_diag": (_ci, [_vp, _vp, _vp]),
+    "lssp_amd_bilu_factor_host": (_ci, [_ci, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lssp_amd_ilu_destroy": (_ci, [_vp]),
     "lssp_amd_ilu_apply": (_ci, [_vp, _vp, _vp, _vp]),
     "lssp_amd_ilu_apply_async": (_ci, [_vp, _vp, _vp, _vp]),

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <thread>
 
+#include "bilu_dev.h"
 #include "internal.h"
 
 using namespace lssp_amd;
@@ -353,7 +354,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10000; }
+int lssp_amd_version(void) { return 10100; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -709,7 +710,11 @@ static int ilu_upload(lssp_amd_ctx *c, lssp_amd_ilu *M)
     // structured ILU(0) of a 5-/7-point grid: line sweeps (linesweep.hip); the
     // packet schedules of the general sweeps are then not needed
     setup_mark(nullptr);
-    const int ls = build_line_sweep(c, M->n, M->Lp, M->Lj, M->Lx, M->Up, M->Uj, M->Ux, M->line);
+    // a BILUK handle always takes the general route: the line apply fuses the L
+    // and U sweeps and has no place for the D stage between them (a bs = 1
+    // BILUK of a grid would otherwise pass for a structured ILU(0))
+    const int ls = M->bs > 0 ? LSSP_AMD_EUNSUPPORTED
+                             : build_line_sweep(c, M->n, M->Lp, M->Lj, M->Lx, M->Up, M->Uj, M->Ux, M->line);
     if (ls != LSSP_AMD_OK && ls != LSSP_AMD_EUNSUPPORTED) return ls;
     setup_mark("line sweeps");
     // line sweeps serve every sweep of a structured factor: the packet and
@@ -749,6 +754,12 @@ static int ilu_upload(lssp_amd_ctx *c, lssp_amd_ilu *M)
     if (fallback) {  // the sync-free sweeps' intermediate vector
         LSSP_HIP(hipMalloc(&M->d_cache, sizeof(double) * std::max(M->n, 1)));
         LSSP_TRY(launch_fill(c, M->d_cache, M->n, TRI_SENTINEL));
+    }
+    if (M->bs > 0) {  // BILUK: the inverted diagonal blocks and the middle stage's output
+        LSSP_HIP(hipMalloc(&M->d_Dinv, sizeof(double) * std::max<size_t>(M->Dinv.size(), 1)));
+        LSSP_HIP(hipMemcpyAsync(M->d_Dinv, M->Dinv.data(), sizeof(double) * M->Dinv.size(), hipMemcpyHostToDevice,
+                                c->stream));
+        LSSP_HIP(hipMalloc(&M->d_mid, sizeof(double) * std::max(M->n, 1)));
     }
     LSSP_HIP(hipStreamSynchronize(c->stream));
     return LSSP_AMD_OK;
@@ -849,6 +860,180 @@ static int ilu_from_factors(lssp_amd_ctx *c, int n, const int *Lp, const int *Lj
     return LSSP_AMD_OK;
 }
 
+// ---- BILUK (pc-biluk.cxx) --------------------------------------------------------
+// steps 1-4 of the setup on the host copy A; c != nullptr and bs <= 8: the
+// numeric block ILU(0) on c's GPU (bilu_factor.hip), else on the host
+static int bilu_factor(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, const double *Ax, int level, int bs,
+                       HostCSR &L, HostCSR &U, std::vector<double> &inv)
+{
+    if (n <= 0 || !Ap || !Aj || !Ax || bs < 1 || bs > BILU_MAX_BS || n % bs != 0) return LSSP_AMD_EINVAL;
+    LSSP_TRY(check_csr(n, n, Ap[n], Ap, Aj));
+    if (Ap[n] < 1) return LSSP_AMD_EINVAL;
+    if (level < 0) level = 1;  // pc.cxx: the reference's default iluk_level
+    setup_mark(nullptr);
+    HostBCSR T;
+    {
+        HostCSR A;
+        A.n = A.ncols = n;
+        A.Ap.assign(Ap, Ap + n + 1);
+        A.Aj.assign(Aj, Aj + Ap[n]);
+        A.Ax.assign(Ax, Ax + Ap[n]);
+        sort_columns(A);  // lssp.cxx:173
+        LSSP_TRY(bilu_pattern(A, level, bs, T));
+    }
+    setup_mark("BILUK copy, BCSR, symbolic");
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    const double t0 = wall_time();
+    const bool dev = c && bs <= BILU_MAX_BS_DEV;
+    LSSP_TRY(dev ? bilu0_factor_gpu(c, T, inv) : bilu0_factor_host(T, inv));
+    if (times)
+        fprintf(stderr, "lssp_amd setup:   BILU(0) numeric (%s path)      %10.6f s\n", dev ? "device" : "host",
+                wall_time() - t0);
+    setup_mark("BILUK numeric");
+    bilu_expand(T, inv, L, U);
+    setup_mark("BILUK expansion to L, U");
+    return LSSP_AMD_OK;
+}
+
+static int bilu_finish(lssp_amd_ctx *c, lssp_amd_ilu *M, std::chrono::steady_clock::time_point t0,
+                       lssp_amd_ilu **out)
+{
+    int st = ilu_upload(c, M);
+    if (st != LSSP_AMD_OK) {
+        lssp_amd_ilu_destroy(M);
+        return st;
+    }
+    M->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *out = M;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_bilu_create(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, const double *Ax, int level, int bs,
+                         lssp_amd_ilu **out)
+{
+    if (!c || !out) return LSSP_AMD_EINVAL;
+    try {
+        LSSP_HIP(hipSetDevice(c->device));
+        auto t0 = std::chrono::steady_clock::now();
+        HostCSR L, U;
+        std::vector<double> inv;
+        LSSP_TRY(bilu_factor(c, n, Ap, Aj, Ax, level, bs, L, U, inv));
+        lssp_amd_ilu *M = new lssp_amd_ilu();
+        M->ctx = c;
+        M->n = n;
+        M->bs = bs;
+        M->Dinv = std::move(inv);
+        M->Lp = std::move(L.Ap);
+        M->Lj = std::move(L.Aj);
+        M->Lx = std::move(L.Ax);
+        M->Up = std::move(U.Ap);
+        M->Uj = std::move(U.Aj);
+        M->Ux = std::move(U.Ax);
+        return bilu_finish(c, M, t0, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+int lssp_amd_bilu_factor_host(int n, const int *Ap, const int *Aj, const double *Ax, int level, int bs, int *nnzL,
+                              int *nnzU, int *Lp, int *Lj, double *Lx, double *Dinv, int *Up, int *Uj, double *Ux)
+{
+    if (!nnzL || !nnzU) return LSSP_AMD_EINVAL;
+    try {
+        if (n <= 0 || !Ap || !Aj || !Ax || bs < 1 || bs > BILU_MAX_BS || n % bs != 0) return LSSP_AMD_EINVAL;
+        if (!Lj) {  // size query: the pattern alone
+            LSSP_TRY(check_csr(n, n, Ap[n], Ap, Aj));
+            if (Ap[n] < 1) return LSSP_AMD_EINVAL;
+            HostCSR A;
+            A.n = A.ncols = n;
+            A.Ap.assign(Ap, Ap + n + 1);
+            A.Aj.assign(Aj, Aj + Ap[n]);
+            A.Ax.assign(Ap[n], 0.0);
+            sort_columns(A);
+            HostBCSR T;
+            LSSP_TRY(bilu_pattern(A, level < 0 ? 1 : level, bs, T));
+            long nl = 0, nu = 0;
+            for (int i = 0; i < T.nb; i++)
+                for (int k = T.Bp[i]; k < T.Bp[i + 1]; k++) {
+                    nl += T.Bj[k] < i;
+                    nu += T.Bj[k] > i;
+                }
+            nl = nl * bs * bs + n;
+            nu = nu * bs * bs + n;
+            if (nl > INT_MAX || nu > INT_MAX) return LSSP_AMD_EINVAL;
+            *nnzL = (int)nl;
+            *nnzU = (int)nu;
+            return LSSP_AMD_OK;
+        }
+        if (!Lp || !Lx || !Dinv || !Up || !Uj || !Ux) return LSSP_AMD_EINVAL;
+        HostCSR L, U;
+        std::vector<double> inv;
+        LSSP_TRY(bilu_factor(nullptr, n, Ap, Aj, Ax, level, bs, L, U, inv));
+        *nnzL = L.Ap[n];
+        *nnzU = U.Ap[n];
+        memcpy(Lp, L.Ap.data(), sizeof(int) * (n + 1));
+        memcpy(Lj, L.Aj.data(), sizeof(int) * L.Aj.size());
+        memcpy(Lx, L.Ax.data(), sizeof(double) * L.Ax.size());
+        memcpy(Up, U.Ap.data(), sizeof(int) * (n + 1));
+        memcpy(Uj, U.Aj.data(), sizeof(int) * U.Aj.size());
+        memcpy(Ux, U.Ax.data(), sizeof(double) * U.Ax.size());
+        memcpy(Dinv, inv.data(), sizeof(double) * inv.size());
+        return LSSP_AMD_OK;
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+// L, D, U as the reference's host setup leaves them in pc.L / pc.D / pc.U: D is
+// the block diagonal as CSR (lssp_pc_biluk_assemble_diag_mat, pc-biluk.cxx:279-314),
+// every row of block i holding the bs columns i*bs .. i*bs + bs-1 in order
+int lssp_amd_ilu_from_ldu(lssp_amd_ctx *c, int n, const int *Lp, const int *Lj, const double *Lx, const int *Dp,
+                          const int *Dj, const double *Dx, const int *Up, const int *Uj, const double *Ux,
+                          lssp_amd_ilu **out)
+{
+    if (!c || !out || n <= 0 || !Lp || !Lj || !Lx || !Dp || !Dj || !Dx || !Up || !Uj || !Ux) return LSSP_AMD_EINVAL;
+    try {
+        LSSP_TRY(check_csr(n, n, Lp[n], Lp, Lj));
+        LSSP_TRY(check_csr(n, n, Up[n], Up, Uj));
+        LSSP_TRY(check_csr(n, n, Dp[n], Dp, Dj));
+        const int bs = Dp[1] - Dp[0];
+        if (bs < 1 || bs > BILU_MAX_BS || n % bs != 0 || (long)Dp[n] != (long)n * bs) return LSSP_AMD_EINVAL;
+        std::vector<double> inv((size_t)n * bs);
+        for (int row = 0; row < n; row++) {
+            const int b0 = row / bs * bs;
+            if (Dp[row + 1] - Dp[row] != bs) return LSSP_AMD_EINVAL;
+            for (int q = 0; q < bs; q++) {
+                if (Dj[Dp[row] + q] != b0 + q) return LSSP_AMD_EINVAL;
+                inv[(size_t)b0 * bs + (size_t)q * bs + (row - b0)] = Dx[Dp[row] + q];
+            }
+        }
+        LSSP_HIP(hipSetDevice(c->device));
+        auto t0 = std::chrono::steady_clock::now();
+        lssp_amd_ilu *M = new lssp_amd_ilu();
+        M->ctx = c;
+        M->n = n;
+        M->bs = bs;
+        M->Dinv = std::move(inv);
+        M->Lp.assign(Lp, Lp + n + 1);
+        M->Lj.assign(Lj, Lj + Lp[n]);
+        M->Lx.assign(Lx, Lx + Lp[n]);
+        M->Up.assign(Up, Up + n + 1);
+        M->Uj.assign(Uj, Uj + Up[n]);
+        M->Ux.assign(Ux, Ux + Up[n]);
+        return bilu_finish(c, M, t0, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+int lssp_amd_ilu_get_diag(const lssp_amd_ilu *M, int *bs, double *Dinv)
+{
+    if (!M || !bs) return LSSP_AMD_EINVAL;
+    *bs = M->bs;
+    if (M->bs > 0 && Dinv) memcpy(Dinv, M->Dinv.data(), sizeof(double) * M->Dinv.size());
+    return LSSP_AMD_OK;
+}
+
 int lssp_amd_ilu_destroy(lssp_amd_ilu *M)
 {
     if (!M) return LSSP_AMD_OK;
@@ -860,6 +1045,8 @@ int lssp_amd_ilu_destroy(lssp_amd_ilu *M)
     for (double *p : M->d_sh)
         if (p) (void)hipFree(p);
     if (M->d_rperm) (void)hipFree(M->d_rperm);
+    if (M->d_Dinv) (void)hipFree(M->d_Dinv);
+    if (M->d_mid) (void)hipFree(M->d_mid);
     delete M;
     return LSSP_AMD_OK;
 }

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <exception>
 
+#include "bilu_dev.h"
 #include "internal.h"
 
 namespace lssp_amd {
@@ -548,6 +549,150 @@ void ilu_factor(lssp_amd_ctx *c, int kind, HostCSR &&A0, int level, double tol, 
     }
     });
     setup_mark("L/U split");
+}
+
+// ---- BILUK (pc-biluk.cxx) ------------------------------------------------------
+// lssp_mat_csr_to_bcsr (matrix-utils.cxx:62-162) followed by the symbolic
+// pattern of pc-biluk.cxx:328-386.  Level 0 keeps A's block pattern as it is
+// (:339-346: a block row without its diagonal block stays without it);
+// level > 0 runs iluk_symbolic on the block graph, which always holds the
+// diagonal, and places A's blocks into it, fill blocks zero.
+int bilu_pattern(const HostCSR &A, int level, int bs, HostBCSR &T)
+{
+    const int n = A.n;
+    if (bs < 1 || n % bs != 0) return LSSP_AMD_EINVAL;
+    const int nb = n / bs, bs2 = bs * bs;
+    HostCSR G;  // the block graph, block columns ascending
+    G.n = G.ncols = nb;
+    G.Ap.assign(nb + 1, 0);
+    std::vector<int> mark(nb, -1), wk;
+    for (int i = 0; i < nb; i++) {
+        wk.clear();
+        for (int k = A.Ap[i * bs]; k < A.Ap[(i + 1) * bs]; k++) {
+            const int b = A.Aj[k] / bs;
+            if (mark[b] != i) {
+                mark[b] = i;
+                wk.push_back(b);
+            }
+        }
+        std::sort(wk.begin(), wk.end());
+        G.Aj.insert(G.Aj.end(), wk.begin(), wk.end());
+        G.Ap[i + 1] = (int)G.Aj.size();
+    }
+    if ((long)G.Aj.size() * bs2 > 0x7fffffffL) return LSSP_AMD_EINVAL;
+    G.Ax.assign(G.Aj.size(), 0.0);
+    HostCSR S = level > 0 ? iluk_symbolic(G, level) : std::move(G);
+    if ((long)S.Aj.size() * bs2 + n > 0x7fffffffL) return LSSP_AMD_EINVAL;  // L, U keep 32-bit row pointers
+    T.nb = nb;
+    T.bs = bs;
+    T.Bp = std::move(S.Ap);
+    T.Bj = std::move(S.Aj);
+    T.Bx.assign(T.Bj.size() * (size_t)bs2, 0.0);
+    std::vector<int> at(nb, -1);
+    for (int i = 0; i < nb; i++) {
+        for (int k = T.Bp[i]; k < T.Bp[i + 1]; k++) at[T.Bj[k]] = k;
+        for (int r = i * bs; r < (i + 1) * bs; r++)
+            for (int k = A.Ap[r]; k < A.Ap[r + 1]; k++) {
+                const int c = A.Aj[k];
+                T.Bx[(size_t)at[c / bs] * bs2 + (c % bs) * bs + r % bs] = A.Ax[k];
+            }
+    }
+    return LSSP_AMD_OK;
+}
+
+// lssp_pc_bilu0_fac (pc-biluk.cxx:198-277) with the arithmetic of bilu_dev.h.
+// A block row without its diagonal block gets the identity as its inverse
+// (what :265-270 intends); a singular diagonal block returns LSSP_AMD_EINVAL.
+int bilu0_factor_host(HostBCSR &T, std::vector<double> &inv)
+{
+    const int nb = T.nb, bs = T.bs, bs2 = bs * bs;
+    inv.assign((size_t)nb * bs2, 0.0);
+    std::vector<const double *> wk(nb, nullptr);
+    std::vector<double> blk(bs2);
+    std::vector<int> piv(bs);
+    for (int i = 0; i < nb; i++) {
+        const int end = T.Bp[i + 1];
+        int k = T.Bp[i];
+        for (; k < end && T.Bj[k] < i; k++) {
+            const int idx = T.Bj[k];
+            double *aik = T.Bx.data() + (size_t)k * bs2;
+            std::copy(aik, aik + bs2, blk.begin());
+            bilu_gemm(blk.data(), inv.data() + (size_t)idx * bs2, 1., aik, 0., bs);
+            for (int q = T.Bp[idx]; q < T.Bp[idx + 1]; q++) wk[T.Bj[q]] = T.Bx.data() + (size_t)q * bs2;
+            for (int j = k + 1; j < end; j++)
+                if (wk[T.Bj[j]]) bilu_gemm(aik, wk[T.Bj[j]], -1., T.Bx.data() + (size_t)j * bs2, 1., bs);
+            for (int q = T.Bp[idx]; q < T.Bp[idx + 1]; q++) wk[T.Bj[q]] = nullptr;
+        }
+        double *d = inv.data() + (size_t)i * bs2;
+        if (k < end && T.Bj[k] == i) {
+            std::copy(T.Bx.data() + (size_t)k * bs2, T.Bx.data() + (size_t)(k + 1) * bs2, d);
+            if (bilu_inverse(d, bs, piv.data())) return LSSP_AMD_EINVAL;
+        } else {
+            for (int r = 0; r < bs; r++) d[(bs + 1) * r] = 1.;
+        }
+    }
+    return LSSP_AMD_OK;
+}
+
+// lssp_pc_bilu_bcsr_to_lu (pc-biluk.cxx:104-196): L = the strict-lower blocks
+// and a unit diagonal LAST, U = a unit diagonal FIRST and inv_i * a_ij for
+// j > i; columns ascending, every entry of a block kept (zeros included).
+void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, HostCSR &U)
+{
+    const int nb = T.nb, bs = T.bs, bs2 = bs * bs, n = nb * bs;
+    L = HostCSR();
+    U = HostCSR();
+    L.n = L.ncols = U.n = U.ncols = n;
+    L.Ap.assign(n + 1, 0);
+    U.Ap.assign(n + 1, 0);
+    for (int i = 0; i < nb; i++) {
+        int nl = 0, nu = 0;
+        for (int k = T.Bp[i]; k < T.Bp[i + 1]; k++) {
+            nl += T.Bj[k] < i;
+            nu += T.Bj[k] > i;
+        }
+        for (int r = 0; r < bs; r++) {
+            L.Ap[i * bs + r + 1] = L.Ap[i * bs + r] + nl * bs + 1;
+            U.Ap[i * bs + r + 1] = U.Ap[i * bs + r] + nu * bs + 1;
+        }
+    }
+    L.Aj.resize(L.Ap[n]);
+    L.Ax.resize(L.Ap[n]);
+    U.Aj.resize(U.Ap[n]);
+    U.Ax.resize(U.Ap[n]);
+    parallel_for(nb, [&](long i0, long i1) {
+        std::vector<double> cache(bs2);
+        for (int i = (int)i0; i < (int)i1; i++) {
+            int ol = 0, ou = 1;
+            for (int r = 0; r < bs; r++) {
+                const int row = i * bs + r;
+                L.Aj[L.Ap[row + 1] - 1] = row;
+                L.Ax[L.Ap[row + 1] - 1] = 1.;
+                U.Aj[U.Ap[row]] = row;
+                U.Ax[U.Ap[row]] = 1.;
+            }
+            for (int k = T.Bp[i]; k < T.Bp[i + 1]; k++) {
+                const int j = T.Bj[k];
+                const double *a = T.Bx.data() + (size_t)k * bs2;
+                if (j < i) {
+                    for (int r = 0; r < bs; r++)
+                        for (int c = 0; c < bs; c++) {
+                            L.Aj[L.Ap[i * bs + r] + ol + c] = j * bs + c;
+                            L.Ax[L.Ap[i * bs + r] + ol + c] = a[c * bs + r];
+                        }
+                    ol += bs;
+                } else if (j > i) {
+                    bilu_gemm(inv.data() + (size_t)i * bs2, a, 1., cache.data(), 0., bs);
+                    for (int r = 0; r < bs; r++)
+                        for (int c = 0; c < bs; c++) {
+                            U.Aj[U.Ap[i * bs + r] + ou + c] = j * bs + c;
+                            U.Ax[U.Ap[i * bs + r] + ou + c] = cache[c * bs + r];
+                        }
+                    ou += bs;
+                }
+            }
+        }
+    }, 256);
 }
 
 // Level analysis + upload of one triangular factor.

@@ -263,6 +263,12 @@ struct lssp_amd_ilu {
     mutable unsigned epoch = 0;
     lssp_amd::LineILU line;  // structured factors: line sweeps (ntiles > 0)
     std::mutex sync_free_mu;  // the sync-free arrays, built on first use (ensure_sync_free)
+    // BILUK (bs > 0): the inverted diagonal blocks, block i column-major at
+    // Dinv + i*bs*bs; the apply runs L^-1, then z = D y (k_bdiag), then U^-1
+    int bs = 0;
+    std::vector<double> Dinv;
+    double *d_Dinv = nullptr;
+    double *d_mid = nullptr;  // z: in the L sweep's schedule order (packets) or natural order (sync-free)
     double setup_seconds = 0;
 };
 
@@ -387,6 +393,22 @@ void ilu_factor(lssp_amd_ctx *c, int kind, HostCSR &&A, int level, double tol, i
                 HostCSR &U, int *status);
 int ilu0_factor_gpu(lssp_amd_ctx *c, int n, int blk, const std::vector<int> &Ap, const std::vector<int> &Aj,
                     std::vector<double> &Ax);
+// BILUK setup (ilu_setup.cpp, bilu_factor.hip): pc-biluk.cxx on the arithmetic of bilu_dev.h
+struct HostBCSR {
+    int nb = 0, bs = 1;
+    std::vector<int> Bp, Bj;  // block rows; block columns ascending
+    std::vector<double> Bx;   // bs x bs blocks, column-major
+};
+// A (columns sorted) to BCSR on the level-k block pattern; EINVAL when n % bs != 0
+int bilu_pattern(const HostCSR &A, int level, int bs, HostBCSR &T);
+// numeric block ILU(0) in place, inv = the inverted diagonal blocks; EINVAL on a
+// singular diagonal block.  The GPU one (bs <= 8) is bitwise the host one.
+int bilu0_factor_host(HostBCSR &T, std::vector<double> &inv);
+int bilu0_factor_gpu(lssp_amd_ctx *c, HostBCSR &T, std::vector<double> &inv);
+void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, HostCSR &U);
+// z = D y of a BILUK apply.  pos != nullptr: y and z are indexed by schedule
+// position, row r at pos[r] (the packet sweeps' shadows); else natural order
+int launch_bdiag(lssp_amd_ctx *c, int n, int bs, const double *Dinv, const int *pos, const double *y, double *z);
 int build_trisched(lssp_amd_ctx *c, int n, const std::vector<int> &Tp, const std::vector<int> &Tj,
                    const std::vector<double> &Tx, bool upper, TriSched &t, const TriSched *prod = nullptr,
                    bool packets = true, bool arrays = true, std::vector<int> *lev_in = nullptr);

@@ -1196,6 +1196,180 @@ int lgmres(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, i
     return LSSP_AMD_OK;
 }
 
+// ---------------------------------------------------------------------------
+// RLGMRES: right-preconditioned LGMRES(m, k) (lssp_solver_lgmres_r,
+// solver-lgmres.cxx:313-604), restated call for call.  Its Arnoldi step is
+// gmres_r's; the cycle's basis grows by one column per cycle up to m + k, and
+// column i >= m is A M^-1 z_{i-m}.  Kept exactly as the reference has it:
+//   * the solve uses kk = i columns (:506), so an exit at beta <= tol drops
+//     the last column;
+//   * after the back substitution i is -1, so the test at :516 always holds and
+//     the update is rg = sum_{i<kk} ym[i] v[i] over the BASIS vectors, also when
+//     kk > m: the augmentation vectors never enter the update (:517-521);
+//   * x += M^-1 rg, and z[outer % k] = rg (:544-548);
+//   * one iteration counter in the message lines, printed per step and once
+//     more after a cycle that did not converge (:494-498, :558-562).
+// ---------------------------------------------------------------------------
+int lgmres_r(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *nits, double *res_out)
+{
+    const double t_start = wall_time();  // the reference driver's lssp_get_time() ("total time")
+    double tol_rel, tol_abs, tol_rb = P.tol_rb;
+    int maxit;
+    defaults(P, tol_rel, tol_abs, maxit);
+    const int mk = P.restart < 0 ? DEF_RESTART : P.restart;
+    const int auk = P.aug_k <= 0 ? 3 : P.aug_k;  // lssp.cxx:6
+    if (tol_rb < 0) tol_rb = DEF_TOL;
+    if (mk <= 0) return LSSP_AMD_EINVAL;
+    const int mmax = mk + auk;
+    if (S_H + 2 * mmax + 2 > NSCAL || mmax > 0x7fff || auk > 0x7fff) return LSSP_AMD_EUNSUPPORTED;
+    if (P.verb >= 2 && R.rank == 0) {
+        lprint("lgmres: restart parameter m: %d\n", mk);
+        lprint("lgmres: aug k: %d\n", auk);
+        lprint("lgmres: maximal iteration: %d\n", maxit);
+        lprint("lgmres: tolerance abs: %g\n", tol_abs);
+        lprint("lgmres: tolerance rel: %g\n", tol_rel);
+        lprint("lgmres: tolerance rbn: %g\n", tol_rb);
+    }
+    double *wj = R.vec(), *rg = R.vec();
+    double *V = R.vec(R.nx * (long)mmax);
+    double *Z = R.vec(R.nx * (long)auk);
+    if (!wj || !rg || !V || !Z) return LSSP_AMD_ENOMEM;
+    auto Vi = [&](int i) { return V + (long)i * R.nx; };
+    auto Zi = [&](int i) { return Z + (long)i * R.nx; };
+    std::vector<double> H((size_t)(mmax + 1) * mmax), gg(mmax + 1), cs(mmax), sn(mmax), ym(mmax, 0.0);
+    auto HG = [&](int row, int col) -> double & { return H[(size_t)row * mmax + col]; };
+    auto axy = [&](double a, const double *src, double *dst) {  // lssp_vec_axy
+        Ew e;
+        e.kind = K_AXY;
+        e.a = a;
+        e.x = src;
+        e.out0 = dst;
+        return R.ew(e);
+    };
+    auto axpby = [&](double a, const double *src, double bb, double *dst) {  // lssp_vec_axpby
+        Ew e;
+        e.kind = K_AXPBY;
+        e.a = a;
+        e.b = bb;
+        e.x = src;
+        e.out0 = dst;
+        return R.ew(e);
+    };
+    // a z that its cycle did not set (kk == 0) reads as zero, not as a pool buffer's old contents
+    LSSP_TRY(launch_fill(R.c, Z, R.nx * (long)auk, 0));
+
+    LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));  // :395
+    LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :398
+    LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :399
+    LSSP_TRY(R.sync(0, 16));
+    const double b_norm = R.h(S_BNORM);
+    tol_rb *= b_norm;
+    double beta = R.h(S_RES);
+    int inner = 0, outer = 0;
+    if (beta <= tol_abs) {  // :401-404
+        *nits = 0;
+        *res_out = beta;
+        return LSSP_AMD_OK;
+    }
+    const double err_rel = beta;
+    double tol = tol_rel * err_rel;
+    if (tol < tol_abs) tol = tol_abs;
+    if (tol < tol_rb) tol = tol_rb;
+
+    while (inner < maxit) {
+        int i, kk;
+        const int m = outer < auk ? mk + outer : mk + auk;  // :422-427
+        std::fill(gg.begin(), gg.end(), 0.0);              // :429-435
+        std::fill(H.begin(), H.end(), 0.0);
+        LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :438
+        LSSP_TRY(R.sync(0, 16));
+        gg[0] = beta = R.h(S_TMP);
+        LSSP_TRY(axy(1 / beta, rg, Vi(0)));  // :439
+        for (i = 0; i < m && inner < maxit; i++) {
+            inner++;
+            LSSP_TRY(R.pc(rg, i < mk ? Vi(i) : Zi(i - mk)));        // :447-454
+            LSSP_TRY(R.spmv(EPI_MXY, 1, rg, 0, nullptr, wj));      // :456
+            LSSP_TRY(R.dot1(wj, Vi(0), R.fin(FIN_STORE, 1, R.T(), -1, S_H)));  // :458, j = 0
+            for (int j = 0; j <= i; j++) {  // :457-464, axpby fused with the next dot / the norm
+                Ew e;
+                e.kind = K_GM_MGS;
+                e.out0 = wj;
+                e.x = Vi(j);
+                e.sidx = S_H + j;
+                e.nred = 1;
+                e.r0a = wj;
+                e.r0b = j < i ? Vi(j + 1) : wj;
+                LSSP_TRY(R.ew(e));
+                if (j < i)
+                    LSSP_TRY(R.fin1(wj, Vi(j + 1), R.fin(FIN_STORE, 1, R.T(), -1, S_H + j + 1)));
+                else
+                    LSSP_TRY(R.fin1(wj, wj, R.fin(FIN_NORM, 1, R.T(), -1, S_H + i + 1)));  // :464
+            }
+            LSSP_TRY(R.sync(0, S_H + i + 2));
+            for (int j = 0; j <= i; j++) HG(j, i) = R.h(S_H + j);
+            const double hij = R.h(S_H + i + 1);
+            HG(i + 1, i) = hij;
+            if (std::fabs(hij) <= BREAKDOWN) {  // :467-470
+                i--;
+                break;
+            } else if (i + 1 < m) {
+                LSSP_TRY(axy(1 / hij, wj, Vi(i + 1)));  // :472
+            }
+            for (int j = 0; j < i; j++) {  // :475-481
+                const double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
+                const double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
+                HG(j, i) = h1;
+                HG(j + 1, i) = h2;
+            }
+            double gma = std::sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));  // :483
+            if (std::fabs(gma) == 0.) gma = 1e-20;
+            cs[i] = HG(i, i) / gma;
+            sn[i] = HG(i + 1, i) / gma;
+            gg[i + 1] = -sn[i] * gg[i];
+            gg[i] = cs[i] * gg[i];
+            HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
+            beta = std::fabs(gg[i + 1]);
+            if (P.verb >= 1 && R.rank == 0)
+                lprint("lgmres: itr: %4d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", inner, beta,
+                       (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
+            if (beta <= tol) break;  // :500-502 (goto solve: i is not advanced)
+        }
+        kk = i;  // :506
+        for (i = kk - 1; i >= 0; i--) {  // :507-512
+            ym[i] = gg[i] / HG(i, i);
+            for (int j = 0; j < i; j++) gg[j] = gg[j] - ym[i] * HG(j, i);
+        }
+        if (kk > 0) {  // :515-549; i == -1 here, so :516 always takes the basis-only sum
+            LSSP_TRY(axy(ym[0], Vi(0), rg));
+            for (i = 1; i < kk; i++) LSSP_TRY(axpby(ym[i], Vi(i), 1, rg));
+            LSSP_TRY(R.pc(wj, rg));         // :544
+            LSSP_TRY(axpby(1, wj, 1, x));   // :545
+            Ew cp;
+            cp.kind = K_COPY;  // :548
+            cp.x = rg;
+            cp.out0 = Zi(outer % auk);
+            LSSP_TRY(R.ew(cp));
+        }
+        if (beta <= tol) break;                                           // :551-553
+        LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :555
+        LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :556
+        LSSP_TRY(R.sync(0, 16));
+        beta = R.h(S_RES);
+        if (P.verb >= 1 && R.rank == 0)
+            lprint("lgmres: itr: %4d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", inner, beta,
+                   (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
+        outer++;
+    }
+    if (P.verb >= 2 && R.rank == 0) {
+        lprint("lgmres: total iteration: %d\n", inner);
+        lprint("lgmres: total time: %g\n", wall_time() - t_start);
+    }
+    LSSP_TRY(R.sync(0, 1));  // the last x update is complete when the call returns
+    *nits = inner;
+    *res_out = beta;
+    return LSSP_AMD_OK;
+}
+
 
 // ===========================================================================
 // The remaining Krylov drivers.  Unlike BiCGSTAB / CG / GMRES, the reference
@@ -2319,7 +2493,8 @@ extern "C" int lssp_amd_solve(lssp_amd_ctx *c, const lssp_amd_mat *A, const lssp
     // M: the rank's own rows (a block-Jacobi block on P ranks), or on P ranks
     // the factors of the whole matrix (the reference's global ILU)
     const bool gpc = !bad_args && M && c->nranks > 1 && M->n == A->n_global && M->n != A->nrows;
-    const bool bad_m = bad_args || (M && M->n != A->nrows && !gpc);
+    // (a BILUK handle is single-rank: pc-biluk.cxx has no block-Jacobi path)
+    const bool bad_m = bad_args || (M && M->n != A->nrows && !gpc) || (M && M->bs > 0 && c->nranks > 1);
     if (c->nranks > 1) {
         // every rank must take the same preconditioner path (none / its own block /
         // the global factors): the global path all-gathers in every apply, so a
@@ -2360,6 +2535,7 @@ extern "C" int lssp_amd_solve(lssp_amd_ctx *c, const lssp_amd_mat *A, const lssp
     case LSSP_AMD_GMRES: st = gmres(R, *prm, x, b, &it, &res); break;
     case LSSP_AMD_RGMRES: st = gmres_r(R, *prm, x, b, &it, &res); break;
     case LSSP_AMD_LGMRES: st = lgmres(R, *prm, x, b, &it, &res); break;
+    case LSSP_AMD_RLGMRES: st = lgmres_r(R, *prm, x, b, &it, &res); break;
     case LSSP_AMD_BICGSAFE: st = bicgsafe(R, *prm, x, b, &it, &res); break;
     case LSSP_AMD_CGS: st = cgs(R, *prm, x, b, &it, &res); break;
     case LSSP_AMD_GPBICG: st = gpbi(R, *prm, x, b, &it, &res, false); break;

@@ -724,7 +724,15 @@ int launch_ilu_apply(lssp_amd_ctx *c, const lssp_amd_ilu *M, double *x, const do
             k_perm<true><<<pg, 256, 0, c->stream>>>(M->d_rperm, rhs, M->lower.bp_perm, n);
         LSSP_HIP(hipGetLastError());
         LSSP_TRY(launch_pk6(c, M->lower, M->d_rperm, M->d_sh[e], M->d_sh[e ^ 1]));
-        LSSP_TRY(launch_pk6(c, M->upper, M->d_sh[e], M->d_sh[2 + e], M->d_sh[2 + (e ^ 1)]));
+        const double *urhs = M->d_sh[e];
+        if (M->bs > 0) {
+            // BILUK: z = D y between the sweeps (pc-biluk.cxx:48), in the L
+            // sweep's schedule order, which is how the U sweep indexes its rhs;
+            // the sentinel-armed shadow is only read
+            LSSP_TRY(launch_bdiag(c, n, M->bs, M->d_Dinv, M->lower.bp_pos, M->d_sh[e], M->d_mid));
+            urhs = M->d_mid;
+        }
+        LSSP_TRY(launch_pk6(c, M->upper, urhs, M->d_sh[2 + e], M->d_sh[2 + (e ^ 1)]));
         // x back to natural order as a gather through the inverse permutation
         // (coalesced stores, scattered loads: faster than scattering the stores)
         if (((uintptr_t)x & 15) == 0)
@@ -735,6 +743,10 @@ int launch_ilu_apply(lssp_amd_ctx *c, const lssp_amd_ilu *M, double *x, const do
         return LSSP_AMD_OK;
     }
     LSSP_TRY(launch_trisolve(c, M->lower, rhs, M->d_cache, x));
+    if (M->bs > 0) {  // BILUK: the same stage in natural order; the U sweep still re-arms the cache
+        LSSP_TRY(launch_bdiag(c, M->n, M->bs, M->d_Dinv, nullptr, M->d_cache, M->d_mid));
+        return launch_trisolve(c, M->upper, M->d_mid, x, M->d_cache);
+    }
     return launch_trisolve(c, M->upper, M->d_cache, x, M->d_cache);
 }
 

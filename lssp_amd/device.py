@@ -18,7 +18,8 @@ GMRES, LGMRES, RGMRES, BICGSTAB, CG = 0, 1, 2, 4, 7
 BICGSAFE, CGS, GPBICG, CR, CRS, BICRSTAB, BICRSAFE, GPBICR, QMRCGSTAB, TFQMR, ORTHOMIN = (
     6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17)  # LSSP_SOLVER_TYPE (type-defs.h:157-178)
 BICGSTABL, IDRS = 5, 18
-ILUK, ILUT = 1, 2                  # LSSP_PC_TYPE (type-defs.h:63-101)
+RLGMRES = 3                        # right-preconditioned LGMRES (lssp_solver_lgmres_r)
+ILUK, ILUT, BILUK = 1, 2, 3        # LSSP_PC_TYPE (type-defs.h:63-101)
 SERIAL, TREE = 0, 1                # reduction order
 
 
@@ -307,6 +308,38 @@ class DILU:
                                             ctypes.byref(h)), "ilu_from_factors")
         return cls(dev, h)
 
+    @classmethod
+    def bilu(cls, dev: Device, Ap, Aj, Ax, bs: int, level: int = 0):
+        """BILUK: block ILU(level) on bs x bs blocks (lssp_amd_bilu_create); the numeric
+        factorization runs on the GPU for bs <= 8"""
+        Ap, Aj, Ax = _i32(Ap), _i32(Aj), _f64(Ax)
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_bilu_create(dev.h, Ap.size - 1, _p(Ap), _p(Aj), _p(Ax), level, bs, ctypes.byref(h)),
+            "bilu_create")
+        return cls(dev, h)
+
+    @classmethod
+    def from_ldu(cls, dev: Device, L, D, U):
+        """BILUK factors as the reference leaves them in pc.L / pc.D / pc.U (D: block diagonal CSR)"""
+        Lp, Lj, Lx = _i32(L[0]), _i32(L[1]), _f64(L[2])
+        Dp, Dj, Dx = _i32(D[0]), _i32(D[1]), _f64(D[2])
+        Up, Uj, Ux = _i32(U[0]), _i32(U[1]), _f64(U[2])
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_ilu_from_ldu(dev.h, Lp.size - 1, _p(Lp), _p(Lj), _p(Lx), _p(Dp), _p(Dj), _p(Dx),
+                                        _p(Up), _p(Uj), _p(Ux), ctypes.byref(h)), "ilu_from_ldu")
+        return cls(dev, h)
+
+    def diag(self):
+        """(bs, Dinv): the block size and the inverted diagonal blocks, block i column-major at
+        Dinv[i*bs*bs:]; (0, None) for an ILUK / ILUT handle"""
+        bs = ctypes.c_int()
+        _ck(self.dev.L.lssp_amd_ilu_get_diag(self.h, ctypes.byref(bs), None), "ilu_get_diag")
+        if bs.value == 0:
+            return 0, None
+        Dinv = np.zeros(self.n * bs.value)
+        _ck(self.dev.L.lssp_amd_ilu_get_diag(self.h, ctypes.byref(bs), _p(Dinv)), "ilu_get_diag")
+        return bs.value, Dinv
+
     def factors(self):
         n = self.n
         Lp, Lj, Lx = np.zeros(n + 1, np.int32), np.zeros(self.nnzL, np.int32), np.zeros(self.nnzL)
@@ -372,6 +405,23 @@ def poisson(dim: int, N: int, row0: int = 0, nrows: int | None = None):
     _ck(L.lssp_amd_poisson_rows(dim, N, row0, nrows, _p(Ap), _p(Aj), _p(Ax)), "poisson_rows")
     nnz = int(Ap[-1])
     return Ap, Aj[:nnz].copy(), Ax[:nnz].copy()
+
+
+def bilu_factor_host(Ap, Aj, Ax, bs: int, level: int = 0):
+    """BILUK's factors by the host path, without a GPU (lssp_amd_bilu_factor_host):
+    ((Lp, Lj, Lx), Dinv, (Up, Uj, Ux))."""
+    L = _lib.load()
+    Ap, Aj, Ax = _i32(Ap), _i32(Aj), _f64(Ax)
+    n = Ap.size - 1
+    nl, nu = ctypes.c_int(), ctypes.c_int()
+    _ck(L.lssp_amd_bilu_factor_host(n, _p(Ap), _p(Aj), _p(Ax), level, bs, ctypes.byref(nl), ctypes.byref(nu),
+                                    None, None, None, None, None, None, None), "bilu_factor_host")
+    Lp, Lj, Lx = np.zeros(n + 1, np.int32), np.zeros(nl.value, np.int32), np.zeros(nl.value)
+    Up, Uj, Ux = np.zeros(n + 1, np.int32), np.zeros(nu.value, np.int32), np.zeros(nu.value)
+    Dinv = np.zeros(n * bs)
+    _ck(L.lssp_amd_bilu_factor_host(n, _p(Ap), _p(Aj), _p(Ax), level, bs, ctypes.byref(nl), ctypes.byref(nu),
+                                    _p(Lp), _p(Lj), _p(Lx), _p(Dinv), _p(Up), _p(Uj), _p(Ux)), "bilu_factor_host")
+    return (Lp, Lj, Lx), Dinv, (Up, Uj, Ux)
 
 
 def sort_columns(Ap, Aj, Ax, ncols=None):
