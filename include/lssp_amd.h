@@ -339,6 +339,57 @@ int lssp_amd_csr_to_bcsr(lssp_amd_ctx *ctx, int n, int nnz, int bs, const int *A
 int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int bnnz, const int *Bp,
                          const int *Bj, const double *Bx, int *nnz, int *Ap, int *Aj, double *Ax);
 
+/* ---- assembly on the device: the rest of matrix-utils.h and the matrix
+ *      handle, for a CSR that already lives in HBM (an assembly kernel's, a
+ *      coo_to_csr or bcsr_to_csr result).  Same conventions as the conversions
+ *      above: device arrays, caller-allocated outputs that do not overlap the
+ *      inputs, structure checked on the device first (LSSP_AMD_EINVAL), results
+ *      bitwise the reference's.  COO in HBM -> lssp_amd_coo_to_csr ->
+ *      lssp_amd_csr_sort_columns_dev -> lssp_amd_mat_from_device ->
+ *      lssp_amd_solve runs without a host copy of the matrix.
+ *      What still goes through the host: the ILU setup (lssp_amd_ilu_create /
+ *      lssp_amd_bilu_create take host arrays, as the reference factors on the
+ *      host; download the CSR for them), and the sliced copy of a windowed
+ *      matrix (see lssp_amd_mat_from_device). */
+/* lssp_mat_csr_is_sorted (matrix-utils.cxx:249-279): *sorted = 0 iff some row
+ * holds neighbours Aj[k-1] > Aj[k] (equal neighbours are sorted); nnz == 0: 1.
+ * Column values are compared only, never used as indices. */
+int lssp_amd_csr_is_sorted(lssp_amd_ctx *ctx, int nrows, int nnz, const int *Ap, const int *Aj, int *sorted);
+/* lssp_mat_bcsr_is_sorted (:217-247): the same over block rows / block columns */
+int lssp_amd_bcsr_is_sorted(lssp_amd_ctx *ctx, int nbrows, int bnnz, const int *Bp, const int *Bj, int *sorted);
+/* lssp_mat_sort_column (:387-481) in place on Aj / Ax, the device form of
+ * lssp_amd_csr_sort_columns: a row without a descending neighbour pair is
+ * left as it is (duplicates included); any other row comes out with ascending
+ * columns, every duplicate column carrying the value of its last occurrence. */
+int lssp_amd_csr_sort_columns_dev(lssp_amd_ctx *ctx, int nrows, int ncols, int nnz, const int *Ap, int *Aj,
+                                  double *Ax);
+/* lssp_mat_adjust_zero_diag (:483-587), n x n: a row without an entry Aj == i
+ * gains (i, 1 * tol), appended and then moved left past the trailing entries
+ * whose column is greater than i (it stops at the first that is not: no sort);
+ * all other entries keep their order.  Two calls: with Mj == NULL only *mnnz =
+ * nnz + number of rows without a diagonal is computed (Mp may be NULL); then
+ * Mp (n + 1), Mj and Mx (*mnnz) are filled. */
+int lssp_amd_csr_adjust_zero_diag(lssp_amd_ctx *ctx, int n, int nnz, const int *Ap, const int *Aj,
+                                  const double *Ax, double tol, int *mnnz, int *Mp, int *Mj, double *Mx);
+/* lssp_mat_get_block_diag (:589-698), n x n, nnz > 0 and blk > 0 (else EINVAL,
+ * asserts there): blk == n copies the matrix; any other blk (greater than n
+ * included) keeps of row i the entries whose column lies in the row's diagonal
+ * block [i/blk*blk, min(that + blk, n)), in order, and gives a row left with
+ * none the single entry (i, 1.0).  Two calls as above. */
+int lssp_amd_csr_get_block_diag(lssp_amd_ctx *ctx, int n, int nnz, const int *Ap, const int *Aj,
+                                const double *Ax, int blk, int *mnnz, int *Mp, int *Mj, double *Mx);
+/* A matrix handle from DEVICE arrays, equal in every observable way to
+ * lssp_amd_mat_upload of the same arrays (layout, bytes, every product and
+ * solve bitwise).  The handle owns device-to-device copies: the caller may
+ * free or reuse its arrays on return.  The SpMV's offset-id coding is built
+ * on the GPU; at most 255 offsets and a few status words cross to the host.
+ * A matrix that is not offset-coded and passes the window test (run on the
+ * GPU) is downloaded ONCE (12 B per entry) for the host routine that lays out
+ * its sliced copy; a matrix that fails it never leaves HBM.  Single rank only:
+ * a distributed matrix comes from lssp_amd_mat_upload_dist. */
+int lssp_amd_mat_from_device(lssp_amd_ctx *ctx, int nrows, int ncols, int nnz, const int *dAp,
+                             const int *dAj, const double *dAx, lssp_amd_mat **A);
+
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);
 /* rows [row0, row0+nrows) of the 5-pt (dim 2) or 7-pt (dim 3) Laplacian */

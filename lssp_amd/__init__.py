@@ -2,7 +2,8 @@
 trisolves, BiCGSTAB / GMRES / CG) behind the reference's API.
 
     from lssp_amd.device import ...   # C-ABI handles (include/lssp_amd.h): Device, DMat, DILU, solve
-    from lssp_amd import convert      # CSR / COO / BCSR conversions and transpose on the device
+    from lssp_amd import convert      # CSR / COO / BCSR conversions, transpose, column sort, adjust_zero_diag,
+                                      # get_block_diag on the device; DMat.from_device takes the result
     from lssp_amd.dist import GlooTransport   # host-staged multi-rank transport
     from lssp_amd.synthetic import thermal_like   # config 5's matrix
 

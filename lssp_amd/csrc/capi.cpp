@@ -153,9 +153,7 @@ void parallel_for(long n, const std::function<void(long, long)> &f, long grain)
 // index of its offset in the ascending table.  Rows are summed exactly as
 // before (same entries, same order): only the way the column is found changes.
 namespace {
-constexpr int DIAG_MAX = 255, DIAG_HS = 1024;
-
-struct OffSet {
+struct OffSet {  // DIAG_MAX, DIAG_HS: internal.h (shared with the device build, convert.hip)
     int key[DIAG_HS];
     unsigned char used[DIAG_HS] = {};
     int count = 0;
@@ -354,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10100; }
+int lssp_amd_version(void) { return 10200; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {

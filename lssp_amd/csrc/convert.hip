@@ -18,12 +18,19 @@
 // in block order) is done by one thread per row, so the order is the same
 // by construction.  These kernels are HBM-bound streaming passes; none of
 // them is on the solve path.
+//
+// Assembly (second half of the file): lssp_mat_csr_is_sorted /
+// _bcsr_is_sorted / _sort_column / _adjust_zero_diag / _get_block_diag
+// (matrix-utils.cxx:217-279, :387-698) on device arrays, and
+// lssp_amd_mat_from_device, which builds the handle lssp_amd_mat_upload
+// (capi.cpp) builds, offset-id coding included, from a CSR in HBM.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "internal.h"
@@ -190,11 +197,31 @@ __global__ __launch_bounds__(CT) void k_bcsr_count(long n, int bs, const int *__
     }
 }
 
-// fill row i, then lssp_mat_sort_column (matrix-utils.cxx:434-471) on it: a
-// row with an inversion is sorted by column and every occurrence of a
-// column takes the value stored last for it (the dense row[] buffer there);
-// a stable insertion sort keeps equal columns in their original order, so
-// that value is the last of each run
+// lssp_mat_sort_column's rule (matrix-utils.cxx:448-471) for ONE row [s, o)
+// that has an inversion: sorted by column, and every occurrence of a column
+// takes the value stored last for it (the dense row[] buffer there); a stable
+// insertion sort keeps equal columns in their original order, so that value
+// is the last of each run.  One thread; rows of up to SORT_THREAD_MAX entries
+// in lssp_amd_csr_sort_columns_dev
+__device__ __forceinline__ void sort_row_last_wins(int *__restrict__ Aj, double *__restrict__ Ax, int s, int o)
+{
+    for (int a = s + 1; a < o; a++) {
+        int c = Aj[a];
+        double v = Ax[a];
+        int b = a - 1;
+        while (b >= s && Aj[b] > c) {
+            Aj[b + 1] = Aj[b];
+            Ax[b + 1] = Ax[b];
+            b--;
+        }
+        Aj[b + 1] = c;
+        Ax[b + 1] = v;
+    }
+    for (int a = o - 1; a > s; a--)
+        if (Aj[a - 1] == Aj[a]) Ax[a - 1] = Ax[a];
+}
+
+// fill row i, then lssp_mat_sort_column (matrix-utils.cxx:434-471) on it
 __global__ __launch_bounds__(CT) void k_bcsr_rows(long n, int bs, const int *__restrict__ Bp,
                                                   const int *__restrict__ Bj, const double *__restrict__ Bx,
                                                   const int *__restrict__ Ap, int *__restrict__ Aj,
@@ -218,21 +245,355 @@ __global__ __launch_bounds__(CT) void k_bcsr_rows(long n, int bs, const int *__r
                 }
             }
         }
-        if (sorted) continue;
-        for (int a = s + 1; a < o; a++) {
-            int c = Aj[a];
-            double v = Ax[a];
-            int b = a - 1;
-            while (b >= s && Aj[b] > c) {
-                Aj[b + 1] = Aj[b];
-                Ax[b + 1] = Ax[b];
-                b--;
-            }
-            Aj[b + 1] = c;
-            Ax[b + 1] = v;
+        if (!sorted) sort_row_last_wins(Aj, Ax, s, o);
+    }
+}
+
+// ---- the rest of matrix-utils.h on device arrays (assembly) ------------------
+
+// first index in v[0, n) whose value is > t (v non-decreasing)
+__device__ __forceinline__ int upper_bound(const int *__restrict__ v, int n, int t)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+        if (v[mid] <= t)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// matrix-utils.cxx:217-279: one thread per entry; a descending neighbour
+// pair counts when both entries lie in one row, i.e. k is no row start (a
+// binary search in Ap, run for descending pairs only, until one is found)
+__global__ __launch_bounds__(CT) void k_is_sorted(long nnz, int nrows, const int *__restrict__ Ap,
+                                                  const int *__restrict__ Aj, int *__restrict__ uns)
+{
+    GRID_STRIDE(k, nnz)
+    {
+        if (k == 0 || Aj[k - 1] <= Aj[k]) continue;
+        if (*(volatile int *)uns) continue;
+        int r = upper_bound(Ap, nrows + 1, (int)k - 1);  // first row pointer >= k
+        if (r > nrows || Ap[r] != (int)k) atomicOr(uns, 1);
+    }
+}
+
+constexpr int SORT_THREAD_MAX = 64;  // longest row one thread checks / sorts by insertion
+
+// the same test, one thread per row of up to SORT_THREAD_MAX entries (a
+// stencil matrix descends at every row boundary, which would send each row
+// of k_is_sorted into its binary search); flag[0]: unsorted, flag[1]: a
+// longer row exists, and k_is_sorted then runs over all entries
+__global__ __launch_bounds__(CT) void k_is_sorted_rows(long nrows, const int *__restrict__ Ap,
+                                                       const int *__restrict__ Aj, int *__restrict__ flag)
+{
+    GRID_STRIDE(i, nrows)
+    {
+        int s = Ap[i], e = Ap[i + 1];
+        if (e - s > SORT_THREAD_MAX) {
+            if (!*(volatile int *)(flag + 1)) atomicOr(flag + 1, 1);
+            continue;
         }
-        for (int a = o - 1; a > s; a--)
-            if (Aj[a - 1] == Aj[a]) Ax[a - 1] = Ax[a];
+        bool sorted = true;
+        for (int a = s + 1; a < e && sorted; a++) sorted = Aj[a - 1] <= Aj[a];
+        if (!sorted && !*(volatile int *)flag) atomicOr(flag, 1);
+    }
+}
+
+// lssp_mat_sort_column, rows of up to SORT_THREAD_MAX entries: checked and
+// sorted in place by their thread; longer rows are left as candidates
+// (cand[i] = length, else 0) for the per-entry passes below
+__global__ __launch_bounds__(CT) void k_sort_short(long nrows, const int *__restrict__ Ap, int *__restrict__ Aj,
+                                                   double *__restrict__ Ax, int *__restrict__ cand)
+{
+    GRID_STRIDE(i, nrows)
+    {
+        int s = Ap[i], e = Ap[i + 1];
+        if (e - s > SORT_THREAD_MAX) {
+            cand[i] = e - s;
+            continue;
+        }
+        cand[i] = 0;
+        bool sorted = true;
+        for (int a = s + 1; a < e && sorted; a++) sorted = Aj[a - 1] <= Aj[a];
+        if (!sorted) sort_row_last_wins(Aj, Ax, s, e);
+    }
+}
+
+// entry t of the candidate rows laid end to end (off = exclusive sum of their
+// lengths, 0 for the other rows): its row, the last with off[row] <= t
+__device__ __forceinline__ int packed_row(const int *__restrict__ off, int nrows, int t)
+{
+    return upper_bound(off, nrows + 1, t) - 1;
+}
+
+// which candidate rows hold a descending pair, one thread per entry
+__global__ __launch_bounds__(CT) void k_long_check(long total, int nrows, const int *__restrict__ off,
+                                                   const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                   int *__restrict__ uns)
+{
+    GRID_STRIDE(t, total)
+    {
+        int r = packed_row(off, nrows, (int)t);
+        int k = Ap[r] + ((int)t - off[r]);
+        if (k > Ap[r] && Aj[k - 1] > Aj[k]) uns[r] = 1;
+    }
+}
+
+// ... and the lengths of those alone (in place; cand[nrows] stays 0)
+__global__ __launch_bounds__(CT) void k_long_len(long nrows, const int *__restrict__ uns, int *__restrict__ cand)
+{
+    GRID_STRIDE(i, nrows)
+    {
+        if (!uns[i]) cand[i] = 0;
+    }
+}
+
+// the unsorted long rows' entries as (row << cbits | column) keys with their
+// values, laid end to end
+__global__ __launch_bounds__(CT) void k_long_keys(long total, int nrows, int cbits, const int *__restrict__ off,
+                                                  const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                  const double *__restrict__ Ax, uint64_t *__restrict__ key,
+                                                  int *__restrict__ idx, double *__restrict__ vx)
+{
+    GRID_STRIDE(t, total)
+    {
+        int r = packed_row(off, nrows, (int)t);
+        int k = Ap[r] + ((int)t - off[r]);
+        key[t] = ((uint64_t)(unsigned)r << cbits) | (uint64_t)(unsigned)Aj[k];
+        idx[t] = (int)t;
+        vx[t] = Ax[k];
+    }
+}
+
+// ... back into their rows after the stable sort: position t of the sorted
+// keys is entry t - off[row] of its row; equal keys kept their input order,
+// so the value stored last for a column is the last of its run
+__global__ __launch_bounds__(CT) void k_long_put(long total, int cbits, const uint64_t *__restrict__ key,
+                                                 const int *__restrict__ idx, const double *__restrict__ vx,
+                                                 const int *__restrict__ off, const int *__restrict__ Ap,
+                                                 int *__restrict__ Aj, double *__restrict__ Ax)
+{
+    GRID_STRIDE(t, total)
+    {
+        uint64_t k = key[t];
+        long lo = t, hi = total;  // last position of k's run: the one before the first key > k
+        while (hi - lo > 1) {
+            long mid = (lo + hi) >> 1;
+            if (key[mid] == k)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        int r = (int)(k >> cbits);
+        int d = Ap[r] + ((int)t - off[r]);
+        Aj[d] = (int)(k & ((1ull << cbits) - 1));
+        Ax[d] = vx[idx[lo]];
+    }
+}
+
+// matrix-utils.cxx:498-532: entries of output row i (one more without a diagonal)
+__global__ __launch_bounds__(CT) void k_azd_count(long n, const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                  int *__restrict__ cnt)
+{
+    GRID_STRIDE(i, n)
+    {
+        int s = Ap[i], e = Ap[i + 1];
+        bool has = false;
+        for (int k = s; k < e; k++) has |= Aj[k] == (int)i;
+        cnt[i] = e - s + (has ? 0 : 1);
+    }
+}
+
+// matrix-utils.cxx:542-582: the row copied in order; (i, 1 * tol), appended
+// to a row without a diagonal, then moves left past the trailing entries whose
+// column is greater and stops at the first that is not
+__global__ __launch_bounds__(CT) void k_azd_fill(long n, const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                 const double *__restrict__ Ax, double tol,
+                                                 const int *__restrict__ Mp, int *__restrict__ Mj,
+                                                 double *__restrict__ Mx)
+{
+    GRID_STRIDE(i, n)
+    {
+        int s = Ap[i], len = Ap[i + 1] - s, o = Mp[i];
+        int p = len;  // where the new entry goes (len: all of the row stays before it)
+        if (Mp[i + 1] - o == len)
+            p = -1;  // has its diagonal
+        else
+            while (p > 0 && Aj[s + p - 1] > (int)i) p--;
+        for (int k = 0; k < len; k++) {
+            int d = o + k + ((p >= 0 && k >= p) ? 1 : 0);
+            Mj[d] = Aj[s + k];
+            Mx[d] = Ax[s + k];
+        }
+        if (p >= 0) {
+            Mj[o + p] = (int)i;
+            Mx[o + p] = 1 * tol;
+        }
+    }
+}
+
+// matrix-utils.cxx:615-647: row i keeps the columns of its own diagonal block
+// [start, end); a row left with none gets one entry
+__device__ __forceinline__ void block_range(long i, int n, int blk, int &start, int &end)
+{
+    long s = i / blk * (long)blk;
+    start = (int)s;
+    end = s + blk < n ? (int)(s + blk) : n;
+}
+
+__global__ __launch_bounds__(CT) void k_bd_count(long n, int blk, const int *__restrict__ Ap,
+                                                 const int *__restrict__ Aj, int *__restrict__ cnt)
+{
+    GRID_STRIDE(i, n)
+    {
+        int start, end, c = 0;
+        block_range(i, (int)n, blk, start, end);
+        for (int k = Ap[i]; k < Ap[i + 1]; k++) c += (Aj[k] >= start && Aj[k] < end) ? 1 : 0;
+        cnt[i] = c ? c : 1;
+    }
+}
+
+// matrix-utils.cxx:659-687
+__global__ __launch_bounds__(CT) void k_bd_fill(long n, int blk, const int *__restrict__ Ap,
+                                                const int *__restrict__ Aj, const double *__restrict__ Ax,
+                                                const int *__restrict__ Mp, int *__restrict__ Mj,
+                                                double *__restrict__ Mx)
+{
+    GRID_STRIDE(i, n)
+    {
+        int start, end, o = Mp[i];
+        block_range(i, (int)n, blk, start, end);
+        for (int k = Ap[i]; k < Ap[i + 1]; k++)
+            if (Aj[k] >= start && Aj[k] < end) {
+                Mj[o] = Aj[k];
+                Mx[o] = Ax[k];
+                o++;
+            }
+        if (o == Mp[i]) {
+            Mj[o] = (int)i;
+            Mx[o] = 1;
+        }
+    }
+}
+
+// ---- the SpMV's offset-id coding built on the device (build_diag_ids, capi.cpp) --
+using lssp_amd::DIAG_HS;
+using lssp_amd::DIAG_MAX;
+constexpr int OFF_EMPTY = INT32_MIN;  // no col - row: columns are >= 0 and rows < INT32_MAX
+// the device-wide set: DIAG_HS hash slots, the number of distinct offsets
+// seen, the overflow flag (a 256th distinct offset), the offsets in arrival order
+constexpr int G_COUNT = DIAG_HS, G_OVER = DIAG_HS + 1, G_LIST = DIAG_HS + 2, G_SIZE = G_LIST + DIAG_MAX;
+
+__device__ __forceinline__ unsigned off_slot(int k) { return ((unsigned)k * 2654435761u) >> 22; }  // 10 bits
+
+__global__ __launch_bounds__(CT) void k_off_init(int *__restrict__ g)
+{
+    for (int t = threadIdx.x; t < G_SIZE; t += CT) g[t] = t < DIAG_HS ? OFF_EMPTY : 0;
+}
+
+// k into the open-addressing set tab; true when this call claimed its slot.
+// A slot is READ first, so a key already present costs no atomic (a stencil's
+// 7 offsets are there after the first rows).  Slots only ever fill, and every
+// inserter of k walks the same probe sequence, so k lands in one slot only.
+// *full (more than DIAG_MAX claims) stops further claims: the set never fills up
+__device__ __forceinline__ bool off_insert(int *tab, const int *full, int k)
+{
+    unsigned h = off_slot(k);
+    for (int p = 0; p < DIAG_HS; p++, h = (h + 1) & (DIAG_HS - 1)) {
+        int cur = *(volatile int *)(tab + h);
+        if (cur == k) return false;
+        if (cur != OFF_EMPTY) continue;
+        if (*(volatile const int *)full > DIAG_MAX) return false;
+        int old = atomicCAS(tab + h, OFF_EMPTY, k);
+        if (old == OFF_EMPTY) return true;
+        if (old == k) return false;
+    }
+    return false;
+}
+
+// distinct col - row of all entries: each block collects its own in an LDS
+// set (70 M entries hit 7 keys: LDS reads, no global traffic), then merges
+// that set into the device-wide one
+__global__ __launch_bounds__(CT) void k_off_collect(long nrows, const int *__restrict__ Ap,
+                                                    const int *__restrict__ Aj, int *__restrict__ g)
+{
+    __shared__ int tab[DIAG_HS];
+    __shared__ int cnt;
+    for (int t = threadIdx.x; t < DIAG_HS; t += CT) tab[t] = OFF_EMPTY;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        if (*(volatile int *)&cnt > DIAG_MAX || *(volatile int *)(g + G_OVER)) break;
+        int e = Ap[i + 1];
+        for (int k = Ap[i]; k < e; k++)
+            if (off_insert(tab, &cnt, Aj[k] - (int)i)) atomicAdd(&cnt, 1);
+    }
+    __syncthreads();
+    if (cnt > DIAG_MAX) {
+        if (threadIdx.x == 0) atomicOr(g + G_OVER, 1);
+        return;
+    }
+    for (int t = threadIdx.x; t < DIAG_HS; t += CT) {
+        int k = tab[t];
+        if (k == OFF_EMPTY || !off_insert(g, g + G_COUNT, k)) continue;
+        int at = atomicAdd(g + G_COUNT, 1);
+        if (at < DIAG_MAX)
+            g[G_LIST + at] = k;
+        else
+            atomicOr(g + G_OVER, 1);
+    }
+}
+
+// Ad[k] = index of col - row in the ascending table off[0, nd)
+__global__ __launch_bounds__(CT) void k_off_ids(long nrows, const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                const int *__restrict__ off, int nd, uint8_t *__restrict__ Ad)
+{
+    __shared__ int tab[DIAG_MAX + 1];
+    for (int t = threadIdx.x; t < nd; t += CT) tab[t] = off[t];
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        int e = Ap[i + 1];
+        for (int k = Ap[i]; k < e; k++) {
+            int o = Aj[k] - (int)i, lo = 0, hi = nd - 1;  // o is in the table by construction
+            while (lo < hi) {
+                int mid = (lo + hi) >> 1;
+                if (tab[mid] < o)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            Ad[k] = (uint8_t)lo;
+        }
+    }
+}
+
+// build_windows' first test (capi.cpp): does some WIN_ROWS-row block's column
+// span exceed WIN_CAP?  One workgroup per block
+__global__ __launch_bounds__(CT) void k_win_wide(long nb, int nrows, const int *__restrict__ Ap,
+                                                 const int *__restrict__ Aj, int *__restrict__ wide)
+{
+    __shared__ int slo, shi;
+    for (long b = blockIdx.x; b < nb; b += gridDim.x) {
+        if (threadIdx.x == 0) slo = INT32_MAX, shi = INT32_MIN;
+        __syncthreads();
+        long r0 = b * lssp_amd::WIN_ROWS, r1 = r0 + lssp_amd::WIN_ROWS < nrows ? r0 + lssp_amd::WIN_ROWS : nrows;
+        int lo = INT32_MAX, hi = INT32_MIN;
+        for (int k = Ap[r0] + threadIdx.x; k < Ap[r1]; k += CT) {
+            lo = min(lo, Aj[k]);
+            hi = max(hi, Aj[k]);
+        }
+        if (lo <= hi) {
+            atomicMin(&slo, lo);
+            atomicMax(&shi, hi);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 && slo <= shi && (long)shi + 1 - (slo & ~1) > lssp_amd::WIN_CAP) atomicOr(wide, 1);
+        __syncthreads();
     }
 }
 
@@ -504,6 +865,273 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *c, int nbrows, int nbcols, int bs, int bn
     k_bcsr_rows<<<grid_for(n), CT, 0, s>>>(n, bs, Bp, Bj, Bx, P, Aj, Ax);
     LSSP_HIP(hipGetLastError());
     LSSP_HIP(hipStreamSynchronize(s));
+    return LSSP_AMD_OK;
+}
+
+// matrix-utils.cxx:249-279 (CSR) and :217-247 (block columns of a BCSR): the same test
+static int is_sorted_dev(lssp_amd_ctx *c, int nrows, int nnz, const int *Ap, const int *Aj, int *sorted)
+{
+    if (!c || nrows < 0 || nnz < 0 || !Ap || !sorted || (nnz > 0 && !Aj)) return LSSP_AMD_EINVAL;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(err, int, 3);  // structure, unsorted, long rows
+    LSSP_HIP(hipMemsetAsync(err, 0, 3 * sizeof(int), s));
+    k_check_ptr<<<grid_for((long)nrows + 1), CT, 0, s>>>(nrows, nnz, Ap, err);
+    TRY(checked(s, err));
+    *sorted = 1;
+    if (nnz == 0) return LSSP_AMD_OK;
+    k_is_sorted_rows<<<grid_for(nrows), CT, 0, s>>>(nrows, Ap, Aj, err + 1);
+    LSSP_HIP(hipGetLastError());
+    int h[2] = {0, 0};
+    LSSP_HIP(hipMemcpyAsync(h, err + 1, sizeof(h), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipStreamSynchronize(s));
+    if (!h[0] && h[1]) {  // rows too long for one thread: every entry by its own
+        k_is_sorted<<<grid_for(nnz), CT, 0, s>>>(nnz, nrows, Ap, Aj, err + 1);
+        LSSP_HIP(hipGetLastError());
+        TRY(fetch(s, err + 1, &h[0]));
+    }
+    *sorted = h[0] ? 0 : 1;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_csr_is_sorted(lssp_amd_ctx *c, int nrows, int nnz, const int *Ap, const int *Aj, int *sorted)
+{
+    return is_sorted_dev(c, nrows, nnz, Ap, Aj, sorted);
+}
+
+int lssp_amd_bcsr_is_sorted(lssp_amd_ctx *c, int nbrows, int bnnz, const int *Bp, const int *Bj, int *sorted)
+{
+    return is_sorted_dev(c, nbrows, bnnz, Bp, Bj, sorted);
+}
+
+// matrix-utils.cxx:387-481, in place
+int lssp_amd_csr_sort_columns_dev(lssp_amd_ctx *c, int nrows, int ncols, int nnz, const int *Ap, int *Aj,
+                                  double *Ax)
+{
+    if (!c || nrows < 0 || nnz < 0 || !Ap || (nnz > 0 && (!Aj || !Ax || ncols <= 0))) return LSSP_AMD_EINVAL;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(err, int, 1);
+    LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    k_check_ptr<<<grid_for((long)nrows + 1), CT, 0, s>>>(nrows, nnz, Ap, err);
+    if (nnz > 0) k_check_idx<<<grid_for(nnz), CT, 0, s>>>(nnz, Aj, ncols, err);
+    TRY(checked(s, err));
+    if (nnz == 0 || nrows == 0) return LSSP_AMD_OK;
+    // rows of up to SORT_THREAD_MAX entries: one thread each
+    SCRATCH(cand, int, (long)nrows + 1);
+    SCRATCH(off, int, (long)nrows + 1);
+    LSSP_HIP(hipMemsetAsync(cand + nrows, 0, sizeof(int), s));
+    k_sort_short<<<grid_for(nrows), CT, 0, s>>>(nrows, Ap, Aj, Ax, cand);
+    TRY(exclusive_sum(S, cand, off, (long)nrows + 1));
+    int total = 0;
+    TRY(fetch(s, off + nrows, &total));
+    if (total == 0) return LSSP_AMD_OK;
+    // longer rows, one thread per entry: which of them are out of order ...
+    SCRATCH(uns, int, nrows);
+    LSSP_HIP(hipMemsetAsync(uns, 0, sizeof(int) * (size_t)nrows, s));
+    k_long_check<<<grid_for(total), CT, 0, s>>>(total, nrows, off, Ap, Aj, uns);
+    k_long_len<<<grid_for(nrows), CT, 0, s>>>(nrows, uns, cand);
+    TRY(exclusive_sum(S, cand, off, (long)nrows + 1));
+    TRY(fetch(s, off + nrows, &total));
+    if (total == 0) return LSSP_AMD_OK;
+    // ... and those through one stable radix sort of (row, column) keys
+    int cbits = bits_for((unsigned)(ncols - 1)), rbits = bits_for((unsigned)(nrows - 1));
+    SCRATCH(key, uint64_t, total);
+    SCRATCH(skey, uint64_t, total);
+    SCRATCH(idx, int, total);
+    SCRATCH(sidx, int, total);
+    SCRATCH(vx, double, total);
+    k_long_keys<<<grid_for(total), CT, 0, s>>>(total, nrows, cbits, off, Ap, Aj, Ax, key, idx, vx);
+    TRY(sort_pairs(S, (const uint64_t *)key, skey, (const int *)idx, sidx, total, cbits + rbits));
+    k_long_put<<<grid_for(total), CT, 0, s>>>(total, cbits, skey, sidx, vx, off, Ap, Aj, Ax);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(s));
+    return LSSP_AMD_OK;
+}
+
+// the two-call protocol shared by adjust_zero_diag and get_block_diag: cnt
+// (n + 1, last 0) summed into the row pointers, *mnnz fetched
+static int sized_rows(Scratch &S, long n, const int *cnt, int *P, int *mnnz)
+{
+    TRY(exclusive_sum(S, cnt, P, n + 1));
+    return fetch(S.s, P + n, mnnz);
+}
+
+// matrix-utils.cxx:483-587
+int lssp_amd_csr_adjust_zero_diag(lssp_amd_ctx *c, int n, int nnz, const int *Ap, const int *Aj, const double *Ax,
+                                  double tol, int *mnnz, int *Mp, int *Mj, double *Mx)
+{
+    if (!c || n <= 0 || nnz < 0 || !Ap || !mnnz || (nnz > 0 && !Aj)) return LSSP_AMD_EINVAL;
+    if (Mj && (!Mp || !Mx || (nnz > 0 && !Ax))) return LSSP_AMD_EINVAL;
+    if ((long)nnz + n > INT32_MAX) return LSSP_AMD_EINVAL;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(err, int, 1);
+    LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    k_check_ptr<<<grid_for((long)n + 1), CT, 0, s>>>(n, nnz, Ap, err);
+    if (nnz > 0) k_check_idx<<<grid_for(nnz), CT, 0, s>>>(nnz, Aj, n, err);
+    TRY(checked(s, err));
+    SCRATCH(cnt, int, (long)n + 1);
+    int *P = Mp;
+    if (!P) {
+        SCRATCH(Pt, int, (long)n + 1);
+        P = Pt;
+    }
+    LSSP_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), s));
+    k_azd_count<<<grid_for(n), CT, 0, s>>>(n, Ap, Aj, cnt);
+    TRY(sized_rows(S, n, cnt, P, mnnz));
+    if (!Mj) return LSSP_AMD_OK;
+    k_azd_fill<<<grid_for(n), CT, 0, s>>>(n, Ap, Aj, Ax, tol, P, Mj, Mx);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(s));
+    return LSSP_AMD_OK;
+}
+
+// matrix-utils.cxx:589-698
+int lssp_amd_csr_get_block_diag(lssp_amd_ctx *c, int n, int nnz, const int *Ap, const int *Aj, const double *Ax,
+                                int blk, int *mnnz, int *Mp, int *Mj, double *Mx)
+{
+    if (!c || n <= 0 || nnz <= 0 || blk <= 0 || !Ap || !Aj || !mnnz) return LSSP_AMD_EINVAL;
+    if (Mj && (!Mp || !Mx || !Ax)) return LSSP_AMD_EINVAL;
+    if ((long)nnz + n > INT32_MAX) return LSSP_AMD_EINVAL;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(err, int, 1);
+    LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    k_check_ptr<<<grid_for((long)n + 1), CT, 0, s>>>(n, nnz, Ap, err);
+    k_check_idx<<<grid_for(nnz), CT, 0, s>>>(nnz, Aj, n, err);
+    TRY(checked(s, err));
+    if (blk == n) {  // :606-613: the matrix itself
+        *mnnz = nnz;
+        if (!Mj) return LSSP_AMD_OK;
+        LSSP_HIP(hipMemcpyAsync(Mp, Ap, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice, s));
+        LSSP_HIP(hipMemcpyAsync(Mj, Aj, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
+        LSSP_HIP(hipMemcpyAsync(Mx, Ax, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
+        LSSP_HIP(hipStreamSynchronize(s));
+        return LSSP_AMD_OK;
+    }
+    SCRATCH(cnt, int, (long)n + 1);
+    int *P = Mp;
+    if (!P) {
+        SCRATCH(Pt, int, (long)n + 1);
+        P = Pt;
+    }
+    LSSP_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), s));
+    k_bd_count<<<grid_for(n), CT, 0, s>>>(n, blk, Ap, Aj, cnt);
+    TRY(sized_rows(S, n, cnt, P, mnnz));
+    if (!Mj) return LSSP_AMD_OK;
+    k_bd_fill<<<grid_for(n), CT, 0, s>>>(n, blk, Ap, Aj, Ax, P, Mj, Mx);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(s));
+    return LSSP_AMD_OK;
+}
+
+// build_diag_ids (capi.cpp) for a CSR in HBM: the same table and byte stream
+static int diag_ids_dev(lssp_amd_ctx *c, lssp_amd_mat *M)
+{
+    M->ndiag = 0;
+    if (M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(g, int, G_SIZE);
+    k_off_init<<<1, CT, 0, s>>>(g);
+    k_off_collect<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Aj, g);
+    LSSP_HIP(hipGetLastError());
+    int head[2 + DIAG_MAX];  // count, overflow, the offsets
+    LSSP_HIP(hipMemcpyAsync(head, g + G_COUNT, sizeof(head), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipStreamSynchronize(s));
+    if (head[1] || head[0] > DIAG_MAX) return LSSP_AMD_OK;  // a 256th distinct offset: not coded
+    std::vector<int> off(head + 2, head + 2 + head[0]);
+    std::sort(off.begin(), off.end());
+    // +32: see build_diag_ids
+    const size_t ad_bytes = (size_t)M->nnz + 32;
+    LSSP_HIP(hipMalloc(&M->Ad, ad_bytes));
+    LSSP_HIP(hipMalloc(&M->d_off, sizeof(int) * off.size()));
+    LSSP_HIP(hipMemsetAsync(M->Ad + M->nnz, 0, 32, s));
+    LSSP_HIP(hipMemcpyAsync(M->d_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, s));
+    k_off_ids<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Aj, M->d_off, (int)off.size(), M->Ad);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(s));
+    M->aux_bytes += (long long)ad_bytes + (long long)sizeof(int) * (long long)off.size();
+    M->ndiag = (int)off.size();
+    M->max_off = 0;
+    for (int o : off) M->max_off = std::max(M->max_off, std::abs(o));
+    M->max_off_int = M->max_off;
+    return LSSP_AMD_OK;
+}
+
+// build_windows (capi.cpp) for a CSR in HBM: the span test runs on the device;
+// only a matrix that passes it is downloaded, once, for the host routine that
+// lays out the sliced copy
+static int windows_dev(lssp_amd_ctx *c, lssp_amd_mat *M)
+{
+    if (M->ndiag > 0 || M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
+    hipStream_t s = c->stream;
+    {
+        Scratch S(s);
+        SCRATCH(wide, int, 1);
+        LSSP_HIP(hipMemsetAsync(wide, 0, sizeof(int), s));
+        const long nb = ((long)M->nrows + lssp_amd::WIN_ROWS - 1) / lssp_amd::WIN_ROWS;
+        k_win_wide<<<(unsigned)std::min<long>(nb, 16384), CT, 0, s>>>(nb, M->nrows, M->Ap, M->Aj, wide);
+        LSSP_HIP(hipGetLastError());
+        int h = 0;
+        TRY(fetch(s, wide, &h));
+        if (h) return LSSP_AMD_OK;
+    }
+    std::vector<int> Ap((size_t)M->nrows + 1), Aj((size_t)M->nnz);
+    std::vector<double> Ax((size_t)M->nnz);
+    LSSP_HIP(hipMemcpyAsync(Ap.data(), M->Ap, sizeof(int) * Ap.size(), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipMemcpyAsync(Aj.data(), M->Aj, sizeof(int) * Aj.size(), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipMemcpyAsync(Ax.data(), M->Ax, sizeof(double) * Ax.size(), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipStreamSynchronize(s));
+    return lssp_amd::build_windows(M, Ap.data(), Aj.data(), Ax.data());
+}
+
+// lssp_amd_mat_upload (capi.cpp) from arrays in HBM
+int lssp_amd_mat_from_device(lssp_amd_ctx *c, int nrows, int ncols, int nnz, const int *dAp, const int *dAj,
+                             const double *dAx, lssp_amd_mat **out)
+{
+    if (!c || !out || nrows < 0 || ncols <= 0 || nnz < 0 || !dAp || (nnz > 0 && (!dAj || !dAx)))
+        return LSSP_AMD_EINVAL;
+    LSSP_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    {
+        Scratch S(s);
+        SCRATCH(err, int, 1);
+        LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+        k_check_ptr<<<grid_for((long)nrows + 1), CT, 0, s>>>(nrows, nnz, dAp, err);
+        if (nnz > 0) k_check_idx<<<grid_for(nnz), CT, 0, s>>>(nnz, dAj, ncols, err);
+        TRY(checked(s, err));
+    }
+    lssp_amd_mat *M = new lssp_amd_mat();
+    M->ctx = c;
+    M->nrows = nrows;
+    M->ncols = ncols;
+    M->nnz = nnz;
+    M->n_global = nrows;
+    auto fill = [&]() -> int {
+        // the handle's own copies, padded as upload_csr (capi.cpp) pads them
+        LSSP_HIP(hipMalloc(&M->Ap, sizeof(int) * ((size_t)nrows + 1)));
+        LSSP_HIP(hipMalloc(&M->Aj, sizeof(int) * ((size_t)nnz + 4)));
+        LSSP_HIP(hipMalloc(&M->Ax, sizeof(double) * ((size_t)nnz + 4)));
+        LSSP_HIP(hipMemcpyAsync(M->Ap, dAp, sizeof(int) * ((size_t)nrows + 1), hipMemcpyDeviceToDevice, s));
+        if (nnz) {
+            LSSP_HIP(hipMemcpyAsync(M->Aj, dAj, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
+            LSSP_HIP(hipMemcpyAsync(M->Ax, dAx, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
+        }
+        TRY(diag_ids_dev(c, M));
+        TRY(windows_dev(c, M));
+        LSSP_HIP(hipStreamSynchronize(s));
+        return LSSP_AMD_OK;
+    };
+    int st = fill();
+    if (st != LSSP_AMD_OK) {
+        lssp_amd_mat_destroy(M);
+        return st;
+    }
+    // as lssp_amd_mat_upload: a measurement only
+    if (lssp_amd::tune_spmv_streams(c, M) != LSSP_AMD_OK) (void)hipGetLastError();
+    *out = M;
     return LSSP_AMD_OK;
 }
 

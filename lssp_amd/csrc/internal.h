@@ -297,6 +297,10 @@ int build_diag_ids(lssp_amd_mat *M, const int *Ap, const int *Aj);
 int build_windows(lssp_amd_mat *M, const int *Ap, const int *Aj, const double *Ax);
 int tune_spmv_streams(lssp_amd_ctx *c, lssp_amd_mat *M);
 constexpr int WIN_ROWS = 1024, WIN_CAP = 16384;
+// diagonal-id coding: at most DIAG_MAX distinct offsets col - row, collected in
+// open-addressing sets of DIAG_HS slots (host: build_diag_ids, capi.cpp;
+// device: lssp_amd_mat_from_device, convert.hip)
+constexpr int DIAG_MAX = 255, DIAG_HS = 1024;
 int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, const double *x,
                 double beta, const double *y, double *z, int nred, const double *w0,
                 const double *w1, long cb = 0, long ce = -1);  // chunks [cb, ce); ce < 0: all

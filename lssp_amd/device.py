@@ -212,12 +212,26 @@ class DMat:
             n_global, row0 = dist
             _ck(dev.L.lssp_amd_mat_upload_dist(dev.h, n_global, row0, Ap.size - 1, _p(Ap), _p(Aj), _p(Ax),
                                                ctypes.byref(h)), "mat_upload_dist")
-        self.h = h
+        self._adopt_handle(dev, h, int(Ap[-1]))
+
+    def _adopt_handle(self, dev: Device, h, nnz: int):
+        self.dev, self.h = dev, h
         dev._adopt(self)
         r0, nl, nh = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         dev.L.lssp_amd_mat_local_rows(h, ctypes.byref(r0), ctypes.byref(nl), ctypes.byref(nh))
         self.row0, self.nrows, self.nhalo = r0.value, nl.value, nh.value
-        self.nnz = int(Ap[-1])
+        self.nnz = nnz
+
+    @classmethod
+    def from_device(cls, dev: Device, nrows: int, ncols: int, nnz: int, Ap: "DIdx", Aj: "DIdx", Ax: "DVec"):
+        """The handle of a CSR that already lives in HBM (lssp_amd_mat_from_device): equal to
+        DMat(dev, Ap, Aj, Ax) of the same arrays; it owns copies, so Ap / Aj / Ax may be freed."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_mat_from_device(dev.h, nrows, ncols, nnz, Ap.ptr, Aj.ptr, Ax.ptr, ctypes.byref(h)),
+            "mat_from_device")
+        self = cls.__new__(cls)
+        self._adopt_handle(dev, h, int(nnz))
+        return self
 
     @property
     def nx(self) -> int:
