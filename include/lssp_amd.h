@@ -350,7 +350,10 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      What still goes through the host: the ILU setup (lssp_amd_ilu_create /
  *      lssp_amd_bilu_create take host arrays, as the reference factors on the
  *      host; download the CSR for them), and the sliced copy of a windowed
- *      matrix (see lssp_amd_mat_from_device). */
+ *      matrix (see lssp_amd_mat_from_device).  Both only when the PATTERN is
+ *      new: new values on the same pattern stay on the device
+ *      (lssp_amd_mat_update_values, and lssp_amd_ilu_refactor for the handles
+ *      it serves, below). */
 /* lssp_mat_csr_is_sorted (matrix-utils.cxx:249-279): *sorted = 0 iff some row
  * holds neighbours Aj[k-1] > Aj[k] (equal neighbours are sorted); nnz == 0: 1.
  * Column values are compared only, never used as indices. */
@@ -389,6 +392,43 @@ int lssp_amd_csr_get_block_diag(lssp_amd_ctx *ctx, int n, int nnz, const int *Ap
  * a distributed matrix comes from lssp_amd_mat_upload_dist. */
 int lssp_amd_mat_from_device(lssp_amd_ctx *ctx, int nrows, int ncols, int nnz, const int *dAp,
                              const int *dAj, const double *dAx, lssp_amd_mat **A);
+
+/* ---- new values on an unchanged pattern (no reference counterpart: the
+ *      reference assembles solver and preconditioner again).  For time-stepping
+ *      and Newton loops: everything that depends on the sparsity pattern alone
+ *      (column coding, window layout, level lists, tiles, stream layout,
+ *      hand-off buffers) is kept, and nothing crosses the host. */
+/* dAx: DEVICE memory, nnz values in the entry order of the arrays the handle
+ * was made from (lssp_amd_mat_upload or lssp_amd_mat_from_device).  Afterwards
+ * every product and solve on A is bitwise that of a fresh handle made from the
+ * same pattern with these values; lssp_amd_mat_layout / _bytes / _info answer
+ * as before.  nnz other than the handle's or a NULL argument: LSSP_AMD_EINVAL;
+ * a distributed matrix: LSSP_AMD_EUNSUPPORTED; A is unchanged in both cases.
+ * Returns when the stream has finished. */
+int lssp_amd_mat_update_values(lssp_amd_ctx *ctx, lssp_amd_mat *A, const double *dAx, int nnz);
+/* Factor M again from the values A holds now, keeping every schedule.
+ * Afterwards lssp_amd_ilu_apply / _apply_async / _trisolve / lssp_amd_solve /
+ * lssp_amd_ilu_get_factors are bitwise those of a fresh
+ * lssp_amd_ilu_create(ILUK, level 0) on the new values (the host copies of the
+ * factor values are refreshed by the next lssp_amd_ilu_get_factors).
+ * Eligible: M from lssp_amd_ilu_create with kind ILUK, level 0 and one block
+ * (blk <= 0 or >= n) that runs the tiled line sweeps
+ * (lssp_amd_ilu_sweep_layout: *line == 1 with 16 x 8 tiles).  Every other handle
+ * -- from_factors / from_ldu, ILUT, level >= 1, block-Jacobi, BILUK, the
+ * one-workgroup sweeps of a small 2-D grid (*lines == ny), general packet-swept
+ * factors -- and a distributed A return LSSP_AMD_EUNSUPPORTED with M unchanged
+ * and usable.
+ * A must be n x n with exactly the factor's pattern (per row: L's strict part,
+ * the diagonal, U's strict part), i.e. column-sorted rows that hold their
+ * diagonal, as the matrix M was created from; compared on the device, a
+ * mismatch returns LSSP_AMD_EINVAL with M unchanged.
+ * The first call builds a plan kept until lssp_amd_ilu_destroy: the factor
+ * pattern, a factor value buffer, the reciprocal pivots and the level lists,
+ * 12 B per entry + 16 B per row of device memory; a handle that is never
+ * refactored allocates none of it.  Returns when the stream has finished.  A
+ * HIP error part-way returns LSSP_AMD_EHIP, after which M may only be
+ * destroyed. */
+int lssp_amd_ilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat *A);
 
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);

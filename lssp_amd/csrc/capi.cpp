@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10200; }
+int lssp_amd_version(void) { return 10300; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -821,6 +821,9 @@ static int ilu_create(lssp_amd_ctx *c, int kind, int n, const int *Ap, const int
     M->Up = std::move(U.Ap);
     M->Uj = std::move(U.Aj);
     M->Ux = std::move(U.Ax);
+    M->c_kind = kind;
+    M->c_level = level;
+    M->c_blk = blk;
     int st = ilu_upload(c, M);
     if (st != LSSP_AMD_OK) {
         lssp_amd_ilu_destroy(M);
@@ -828,6 +831,52 @@ static int ilu_create(lssp_amd_ctx *c, int kind, int n, const int *Ap, const int
     }
     M->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     *out = M;
+    return LSSP_AMD_OK;
+}
+
+// New values on the same pattern: the numeric ILU(0) again (k_ilu0_level over
+// the kept level lists) and both coefficient streams rewritten from it
+// (k_coef_refill); tiles, stream layout, hand-off buffers and claim counters
+// stay as ilu_create left them.
+int lssp_amd_ilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A)
+{
+    if (!c || !M || !A) return LSSP_AMD_EINVAL;
+    const LineILU &li = M->line;
+    const bool eligible = M->c_kind == LSSP_AMD_ILUK && M->c_level == 0 && (M->c_blk <= 0 || M->c_blk >= M->n) &&
+                          M->bs == 0 && li.ntiles > 0 && li.kind == 0 && li.g2 == 0 && li.P * li.NJ <= 256;
+    if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
+    if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
+    if ((long)A->nnz != (long)M->Lp[M->n] + M->Up[M->n] - M->n) return LSSP_AMD_EINVAL;
+    // LSSP_AMD_SETUP_TIMES=1: the phases' own durations (the stream drained after each)
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    try {
+        LSSP_HIP(hipSetDevice(c->device));
+        double t0 = wall_time();
+        auto mark = [&](const char *phase) {  // microseconds: a phase here is far below setup_mark's 1 ms
+            const double t = wall_time();
+            if (times) fprintf(stderr, "lssp_amd refactor: %-20s %10.6f s\n", phase, t - t0);
+            t0 = t;
+        };
+        LSSP_TRY(refactor_plan_build(c, M));
+        mark("plan");
+        int same = 0;
+        LSSP_TRY(refactor_same_pattern(c, *M->rf, M->n, A->Ap, A->Aj, &same));
+        if (!same) return LSSP_AMD_EINVAL;
+        mark("pattern compare");
+        LSSP_TRY(refactor_numeric(c, *M->rf, M->n, A->Ax));
+        M->host_stale = true;
+        if (times) LSSP_HIP(hipStreamSynchronize(c->stream));
+        mark("numeric ILU(0)");
+        LSSP_TRY(launch_line_refill(c, M->line, M->n, M->rf->d_Fp, M->rf->d_Fj, M->rf->d_Fx));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        mark("coefficient streams");
+        if (times)  // the refill's traffic: each sweep reads F once and writes every slot of its stream
+            fprintf(stderr, "lssp_amd refactor: refill bytes %lld\n",
+                    2 * (4LL * (M->n + 1) + 12LL * M->rf->nnz) +
+                        8LL * (li.L.rows_total * li.L.NA + li.U.rows_total * li.U.NA));
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
     return LSSP_AMD_OK;
 }
 
@@ -1039,6 +1088,7 @@ int lssp_amd_ilu_destroy(lssp_amd_ilu *M)
     free_trisched(M->lower);
     free_trisched(M->upper);
     free_line_sweep(M->line);
+    refactor_plan_free(M->rf);
     if (M->d_cache) (void)hipFree(M->d_cache);
     for (double *p : M->d_sh)
         if (p) (void)hipFree(p);
@@ -1130,6 +1180,8 @@ int lssp_amd_ilu_get_factors(const lssp_amd_ilu *M, int *Lp, int *Lj, double *Lx
                              double *Ux)
 {
     if (!M) return LSSP_AMD_EINVAL;
+    // after lssp_amd_ilu_refactor the host copies of the values are brought up to date here
+    if (Lx || Ux) LSSP_TRY(refactor_host_factors(const_cast<lssp_amd_ilu *>(M)));
     if (Lp) memcpy(Lp, M->Lp.data(), sizeof(int) * M->Lp.size());
     if (Lj) memcpy(Lj, M->Lj.data(), sizeof(int) * M->Lj.size());
     if (Lx) memcpy(Lx, M->Lx.data(), sizeof(double) * M->Lx.size());

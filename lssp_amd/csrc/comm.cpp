@@ -452,6 +452,7 @@ int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal
     M->nnz = nnz;
     M->n_global = n_global;
     M->row0 = row0;
+    M->dist = true;
     {  // the longest run of chunks without a halo-reading row (spmv_halo)
         const long nch = num_chunks(nlocal);
         long run0 = 0, best0 = 0, best1 = 0;

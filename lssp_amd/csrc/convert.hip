@@ -597,6 +597,31 @@ __global__ __launch_bounds__(CT) void k_win_wide(long nb, int nrows, const int *
     }
 }
 
+// The values of a windowed matrix's sliced copy (build_windows, capi.cpp) from
+// its CSR values.  Thread t of 1024-row block b is lane l = t % 64 of slice
+// 16 b + t / 64; s_row[1024 b + t] = its row in the block | that row's length
+// << 10; entry k of the row goes to s_ax[s_meta[2 slice] + 64 k + l], so a wave
+// writes 64 consecutive doubles per k.  Slots past a row's length (padding to
+// the slice's longest row) are not touched: they hold +0.0 from the build.
+__global__ __launch_bounds__(CT) void k_sell_refill(long nb, int nrows, const int *__restrict__ Ap,
+                                                    const uint32_t *__restrict__ s_row,
+                                                    const int *__restrict__ s_meta, const double *__restrict__ Ax,
+                                                    double *__restrict__ s_ax)
+{
+    GRID_STRIDE(g, nb * lssp_amd::WIN_ROWS)
+    {
+        const uint32_t rw = s_row[g];
+        const long row = g / lssp_amd::WIN_ROWS * lssp_amd::WIN_ROWS + (rw & (lssp_amd::WIN_ROWS - 1));
+        if (row >= nrows) continue;
+        const long slice = g / 64;
+        const int l = (int)(g % 64), e0 = Ap[row];
+        // the row's length as the layout was built for it, never past the slice's padded length
+        const int len = min(min((int)(rw >> 10), Ap[row + 1] - e0), s_meta[2 * slice + 1]);
+        double *dst = s_ax + s_meta[2 * slice] + l;
+        for (int k = 0; k < len; k++) dst[64L * k] = Ax[e0 + k];
+    }
+}
+
 // temporary device memory of one call, released after the stream drains
 struct Scratch {
     hipStream_t s;
@@ -1132,6 +1157,28 @@ int lssp_amd_mat_from_device(lssp_amd_ctx *c, int nrows, int ncols, int nnz, con
     // as lssp_amd_mat_upload: a measurement only
     if (lssp_amd::tune_spmv_streams(c, M) != LSSP_AMD_OK) (void)hipGetLastError();
     *out = M;
+    return LSSP_AMD_OK;
+}
+
+// New values on the same pattern.  The offset ids, the window spans and the
+// sliced copy's columns and row order depend on the pattern alone: the values
+// are copied into the resident Ax and, for a windowed matrix, into the sliced
+// copy's value slots (k_sell_refill); its padding slots stay +0.0.
+int lssp_amd_mat_update_values(lssp_amd_ctx *c, lssp_amd_mat *A, const double *dAx, int nnz)
+{
+    if (!c || !A || !dAx || nnz != A->nnz) return LSSP_AMD_EINVAL;
+    if (A->dist) return LSSP_AMD_EUNSUPPORTED;
+    if (nnz == 0) return LSSP_AMD_OK;
+    LSSP_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    LSSP_HIP(hipMemcpyAsync(A->Ax, dAx, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
+    if (A->d_win) {
+        const long nb = ((long)A->nrows + lssp_amd::WIN_ROWS - 1) / lssp_amd::WIN_ROWS;
+        k_sell_refill<<<grid_for(nb * lssp_amd::WIN_ROWS), CT, 0, s>>>(nb, A->nrows, A->Ap, A->s_row, A->s_meta, A->Ax,
+                                                                      A->s_ax);
+        LSSP_HIP(hipGetLastError());
+    }
+    LSSP_HIP(hipStreamSynchronize(s));
     return LSSP_AMD_OK;
 }
 

@@ -65,6 +65,30 @@ __global__ __launch_bounds__(256) void k_ilu0_level(const int *__restrict__ rows
     dinv[i] = 1. / d;
 }
 
+// levels of the strict-lower DAG (row i waits on rows C[k] < i of its sorted
+// row): rows ordered by level, level l at rows[off[l] .. off[l + 1])
+static int level_lists(int n, const std::vector<int> &Ap, const std::vector<int> &Aj, std::vector<int> &off,
+                       std::vector<int> &rows)
+{
+    std::vector<int> lev(n, 0);
+    int nlev = 0;
+    for (int i = 0; i < n; i++) {
+        int l = 0;
+        for (int k = Ap[i]; k < Ap[i + 1] && Aj[k] < i; k++) l = std::max(l, lev[Aj[k]] + 1);
+        lev[i] = l;
+        nlev = std::max(nlev, l + 1);
+    }
+    off.assign(nlev + 1, 0);
+    rows.resize(n);
+    for (int i = 0; i < n; i++) off[lev[i] + 1]++;
+    for (int l = 0; l < nlev; l++) off[l + 1] += off[l];
+    {
+        std::vector<int> fill(off.begin(), off.end() - 1);
+        for (int i = 0; i < n; i++) rows[fill[lev[i]]++] = i;
+    }
+    return nlev;
+}
+
 // In place on the host CSR (sorted rows): upload, level-scheduled launches,
 // download of the values.  blk: block size of a block-diagonal matrix (n: one
 // block).
@@ -74,22 +98,8 @@ int ilu0_factor_gpu(lssp_amd_ctx *c, int n, int blk, const std::vector<int> &Ap,
     if (n <= 0) return LSSP_AMD_OK;
     if (blk <= 0 || blk > n) blk = n;
     const long nnz = Ap[n];
-    // levels of the strict-lower DAG; row i waits on rows C[k] < i of its row
-    std::vector<int> lev(n, 0);
-    int nlev = 0;
-    for (int i = 0; i < n; i++) {
-        int l = 0;
-        for (int k = Ap[i]; k < Ap[i + 1] && Aj[k] < i; k++) l = std::max(l, lev[Aj[k]] + 1);
-        lev[i] = l;
-        nlev = std::max(nlev, l + 1);
-    }
-    std::vector<int> off(nlev + 1, 0), rows(n);
-    for (int i = 0; i < n; i++) off[lev[i] + 1]++;
-    for (int l = 0; l < nlev; l++) off[l + 1] += off[l];
-    {
-        std::vector<int> fill(off.begin(), off.end() - 1);
-        for (int i = 0; i < n; i++) rows[fill[lev[i]]++] = i;
-    }
+    std::vector<int> off, rows;
+    const int nlev = level_lists(n, Ap, Aj, off, rows);
     int *d_Ap = nullptr, *d_Aj = nullptr, *d_rows = nullptr;
     double *d_Ax = nullptr, *d_dinv = nullptr;
     int st = LSSP_AMD_OK;
@@ -123,6 +133,128 @@ int ilu0_factor_gpu(lssp_amd_ctx *c, int n, int blk, const std::vector<int> &Ap,
     for (void *p : {(void *)d_Ap, (void *)d_Aj, (void *)d_Ax, (void *)d_rows, (void *)d_dinv})
         if (p) (void)hipFree(p);
     return st;
+}
+
+// ---------------------------------------------------------------------------
+// lssp_amd_ilu_refactor: the same factorization on buffers that stay on the
+// device (RefactorPlan, internal.h)
+// ---------------------------------------------------------------------------
+// *diff |= 1 when the CSR pattern (Ap, Aj) is not the plan's (Fp, Fj); the
+// entry counts are equal (checked on the host), so one index space serves both
+__global__ __launch_bounds__(256) void k_pattern_diff(long n1, long nnz, const int *__restrict__ Ap,
+                                                      const int *__restrict__ Fp, const int *__restrict__ Aj,
+                                                      const int *__restrict__ Fj, int *__restrict__ diff)
+{
+    const long m = n1 > nnz ? n1 : nnz;
+    bool d = false;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < m; i += (long)gridDim.x * 256) {
+        if (i < n1) d |= Ap[i] != Fp[i];
+        if (i < nnz) d |= Aj[i] != Fj[i];
+    }
+    if (d) atomicOr(diff, 1);
+}
+
+void refactor_plan_free(RefactorPlan *p)
+{
+    if (!p) return;
+    for (void *q : {(void *)p->d_Fp, (void *)p->d_Fj, (void *)p->d_Fx, (void *)p->d_dinv, (void *)p->d_rows,
+                    (void *)p->d_flag})
+        if (q) (void)hipFree(q);
+    delete p;
+}
+
+// F's row i = L's strict entries, the diagonal, U's strict entries (L keeps its
+// unit diagonal LAST, U its pivot FIRST): the pattern ilu_factor split them from
+int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M)
+{
+    if (M->rf) return LSSP_AMD_OK;
+    const int n = M->n;
+    const long nnz = (long)M->Lp[n] + M->Up[n] - n;
+    std::vector<int> Fp(n + 1), Fj((size_t)nnz);
+    Fp[0] = 0;
+    for (int i = 0; i < n; i++) Fp[i + 1] = Fp[i] + (M->Lp[i + 1] - M->Lp[i] - 1) + (M->Up[i + 1] - M->Up[i]);
+    parallel_for(n, [&](long i0, long i1) {
+        for (long i = i0; i < i1; i++) {
+            int f = Fp[i];
+            for (int k = M->Lp[i]; k < M->Lp[i + 1] - 1; k++) Fj[f++] = M->Lj[k];
+            for (int k = M->Up[i]; k < M->Up[i + 1]; k++) Fj[f++] = M->Uj[k];
+        }
+    });
+    RefactorPlan *p = new RefactorPlan();
+    p->nnz = nnz;
+    std::vector<int> rows;
+    level_lists(n, Fp, Fj, p->lev_off, rows);
+    auto fill = [&]() -> int {
+        LSSP_HIP(hipMalloc(&p->d_Fp, sizeof(int) * (n + 1)));
+        LSSP_HIP(hipMalloc(&p->d_Fj, sizeof(int) * nnz));
+        LSSP_HIP(hipMalloc(&p->d_Fx, sizeof(double) * nnz));
+        LSSP_HIP(hipMalloc(&p->d_dinv, sizeof(double) * n));
+        LSSP_HIP(hipMalloc(&p->d_rows, sizeof(int) * n));
+        LSSP_HIP(hipMalloc(&p->d_flag, sizeof(int)));
+        LSSP_HIP(hipMemcpyAsync(p->d_Fp, Fp.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, c->stream));
+        LSSP_HIP(hipMemcpyAsync(p->d_Fj, Fj.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, c->stream));
+        LSSP_HIP(hipMemcpyAsync(p->d_rows, rows.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        return LSSP_AMD_OK;
+    };
+    const int st = fill();
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        refactor_plan_free(p);
+        return st;
+    }
+    M->rf = p;
+    return LSSP_AMD_OK;
+}
+
+int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same)
+{
+    LSSP_HIP(hipMemsetAsync(p.d_flag, 0, sizeof(int), c->stream));
+    const long m = std::max<long>(n + 1, p.nnz);
+    k_pattern_diff<<<(unsigned)std::min<long>((m + 255) / 256, 16384), 256, 0, c->stream>>>(n + 1, p.nnz, dAp, p.d_Fp,
+                                                                                          dAj, p.d_Fj, p.d_flag);
+    LSSP_HIP(hipGetLastError());
+    int diff = 0;
+    LSSP_HIP(hipMemcpyAsync(&diff, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    *same = !diff;
+    return LSSP_AMD_OK;
+}
+
+// ilu0_factor_gpu's launches on the plan's buffers (one block: blk = n)
+int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx)
+{
+    LSSP_HIP(hipMemcpyAsync(p.d_Fx, dAx, sizeof(double) * p.nnz, hipMemcpyDeviceToDevice, c->stream));
+    const int nlev = (int)p.lev_off.size() - 1;
+    for (int l = 0; l < nlev; l++) {
+        const int cnt = p.lev_off[l + 1] - p.lev_off[l];
+        k_ilu0_level<<<(cnt + 255) / 256, 256, 0, c->stream>>>(p.d_rows + p.lev_off[l], cnt, p.d_Fp, p.d_Fj, p.d_Fx,
+                                                              p.d_dinv, n);
+    }
+    LSSP_HIP(hipGetLastError());
+    return LSSP_AMD_OK;
+}
+
+// the host copies Lx / Ux from the device factors (ilu_factor's split)
+int refactor_host_factors(lssp_amd_ilu *M)
+{
+    if (!M->host_stale || !M->rf) return LSSP_AMD_OK;
+    lssp_amd_ctx *c = M->ctx;
+    const int n = M->n;
+    std::vector<double> Fx((size_t)M->rf->nnz);
+    LSSP_HIP(hipMemcpyAsync(Fx.data(), M->rf->d_Fx, sizeof(double) * Fx.size(), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    parallel_for(n, [&](long i0, long i1) {
+        for (long i = i0; i < i1; i++) {
+            const int nl = M->Lp[i + 1] - M->Lp[i] - 1, nu = M->Up[i + 1] - M->Up[i];
+            size_t f = (size_t)(M->Lp[i] - i) + (size_t)M->Up[i];  // strict L entries + U entries of the rows before
+            for (int q = 0; q < nl; q++) M->Lx[M->Lp[i] + q] = Fx[f + q];
+            M->Lx[M->Lp[i + 1] - 1] = 1;
+            for (int q = 0; q < nu; q++) M->Ux[M->Up[i] + q] = Fx[f + nl + q];
+        }
+    });
+    M->host_stale = false;
+    return LSSP_AMD_OK;
 }
 
 }  // namespace lssp_amd

@@ -145,6 +145,7 @@ struct lssp_amd_mat {
     int streams = 0;
     // distributed layout
     int n_global = 0, row0 = 0, nhalo = 0;
+    bool dist = false;  // made by lssp_amd_mat_upload_dist (any rank count)
     // halo exchange plan: for each peer, indices (local) to send and the count to receive
     std::vector<int> send_peer, send_off, send_cnt;  // host plan
     std::vector<int> recv_peer, recv_off, recv_cnt;  // recv_off relative to the halo region
@@ -247,6 +248,19 @@ struct LineILU {
     double *d_g2L = nullptr, *d_g2U = nullptr;
 };
 
+// lssp_amd_ilu_refactor's state (ilu_factor.hip): the factor pattern F (row i =
+// L's strict part, the diagonal, U's strict part: the matrix's own pattern) and
+// the buffers k_ilu0_level works in, kept between refactors.  4 + 8 B per
+// entry, 4 + 8 + 4 B per row.
+struct RefactorPlan {
+    long nnz = 0;
+    int *d_Fp = nullptr, *d_Fj = nullptr;
+    double *d_Fx = nullptr, *d_dinv = nullptr;
+    int *d_rows = nullptr;     // rows ordered by level of the strict-lower DAG
+    std::vector<int> lev_off;  // host: d_rows[lev_off[l] .. lev_off[l + 1]) is level l
+    int *d_flag = nullptr;     // the pattern compare's answer
+};
+
 }  // namespace lssp_amd
 
 struct lssp_amd_ilu {
@@ -270,6 +284,11 @@ struct lssp_amd_ilu {
     double *d_Dinv = nullptr;
     double *d_mid = nullptr;  // z: in the L sweep's schedule order (packets) or natural order (sync-free)
     double setup_seconds = 0;
+    // how the handle was made (lssp_amd_ilu_refactor's eligibility test):
+    // c_kind 0 = caller-made factors (from_factors / from_ldu / BILUK)
+    int c_kind = 0, c_level = 0, c_blk = 0;
+    lssp_amd::RefactorPlan *rf = nullptr;  // built by the first lssp_amd_ilu_refactor
+    bool host_stale = false;  // Lx / Ux are older than the device factors (refreshed by get_factors)
 };
 
 namespace lssp_amd {
@@ -448,6 +467,17 @@ int launch_linefill_apply_tail(lssp_amd_ctx *c, const LineILU &li, double *x, co
                                long *tail_waves);
 int launch_linefill_sweep(lssp_amd_ctx *c, const LineILU &li, int which, double *x, const double *rhs);
 void free_line_sweep(LineILU &li);
+// lssp_amd_ilu_refactor (capi.cpp).  ilu_factor.hip: the plan from the host
+// copies of the factor pattern; *same = A's device pattern equals it; the
+// numeric ILU(0) of Ax (device, plan order) into d_Fx; Lx / Ux from d_Fx.
+int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M);
+void refactor_plan_free(RefactorPlan *p);
+int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same);
+int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx);
+int refactor_host_factors(lssp_amd_ilu *M);
+// linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
+// the factored values Fx on the pattern (Fp, Fj); every slot is written
+int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);
 int launch_line_apply(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs);
 // the apply followed by z = op(A x) (+ fused dots), the product run by the U
 // sweep's workgroups as planes of x become final (k_line2 tail); results are

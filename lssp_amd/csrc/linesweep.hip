@@ -395,6 +395,102 @@ int line_rearm(lssp_amd_ctx *c, LineILU &li)
     return launch_fill(c, li.d_hj, li.hj_n, TRI_SENTINEL);
 }
 
+// ---------------------------------------------------------------------------
+// lssp_amd_ilu_refactor: CoefSrc::build + upload_sweep on the device
+// ---------------------------------------------------------------------------
+// One thread per stream slot.  Tile blockIdx.x; blockIdx.y takes a contiguous
+// range of the tile's steps, in chunks of two steps (P * nj <= 128 slots each,
+// laid out back to back as upload_sweep does: slot = step * P * nj + p * nj + l).
+// A slot valid at its step (row i = s - l - p - sigma(p) on the line) reads its
+// row of the factored matrix F (pattern Fp / Fj: the grid neighbours,
+// ascending) and takes the entries on its sweep's side of the diagonal by
+// their offset -- plane: component 0, nx: 1, 1: 2 -- and, NA == 4, the pivot
+// (U) or the unit diagonal (L); a missing neighbour and every slot not valid at
+// its step are +0.0.  The U sweep's tiles are in mirrored coordinates: sweep
+// row r_s is natural row n-1 - r_s.  A thread keeps its (p, l) over the chunks,
+// so consecutive chunks read rows i, i + 2, ... of one line (the same cache
+// lines of F while they are warm); the chunk's NA doubles per slot go through
+// LDS and leave as one run of consecutive doubles, 64 per wave store.  Every
+// slot of every tile is written, so nothing of the previous values survives.
+template <int NA>
+__global__ __launch_bounds__(256) void k_coef_refill(const LineTile *__restrict__ tiles, int nx, int ny, long n,
+                                                     long plane, int P, int LV, int upper,
+                                                     const int *__restrict__ Fp, const int *__restrict__ Fj,
+                                                     const double *__restrict__ Fx, double *__restrict__ coef)
+{
+    __shared__ double buf[256 * NA];
+    const LineTile t = tiles[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int blk = P * t.nj;            // slots per step (<= 256: launch_line_refill)
+    const int spc = blk <= 128 ? 2 : 1;  // steps per chunk
+    const int so = tid >= blk ? 1 : 0, rem = tid - so * blk, p = rem / t.nj, l = rem - p * t.nj;
+    const int sg = LV >= 2 ? (LV - 1) * (p / 4) : 0;  // line_sigma
+    const bool mine = tid < spc * blk && p < t.np;    // a plane of the tile (else +0.0 at every step)
+    const long line0 = mine ? ((long)(t.k0 + p) * ny + (t.j0 + l)) * nx : 0;
+    const int nchunk = (t.T + spc - 1) / spc, per = (nchunk + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int c0 = blockIdx.y * per, c1 = min(nchunk, c0 + per);
+    for (int ch = c0; ch < c1; ch++) {
+        const int nslot = min(spc, t.T - ch * spc) * blk;
+        const int i = ch * spc + so - l - p - sg;
+        double ck = 0., cj = 0., ci = 0., cd = 0.;
+        if (mine && tid < nslot && i >= 0 && i < nx) {  // step_range
+            const long r = upper ? n - 1 - (line0 + i) : line0 + i;
+            const int b = Fp[r], e = Fp[r + 1];
+            // a grid row holds at most 7 entries: all loads issued before the first is used
+            int fj[7];
+            double fx[7];
+#pragma unroll
+            for (int u = 0; u < 7; u++) {
+                const bool in = b + u < e;
+                fj[u] = in ? Fj[b + u] : (int)r;
+                fx[u] = in ? Fx[b + u] : 0.;
+            }
+#pragma unroll
+            for (int u = 0; u < 7; u++) {
+                const long off = upper ? (long)fj[u] - r : r - (long)fj[u];
+                if (b + u >= e) continue;
+                if (off > 0) {
+                    if (off == plane) ck = fx[u];
+                    else if (off == nx) cj = fx[u];
+                    else ci = fx[u];
+                } else if (off == 0) {
+                    cd = upper ? fx[u] : 1.;
+                }
+            }
+        }
+        if (tid < nslot) {
+            buf[tid * NA] = ck;
+            buf[tid * NA + 1] = cj;
+            buf[tid * NA + 2] = ci;
+            if (NA == 4) buf[tid * NA + 3] = cd;
+        }
+        __syncthreads();
+        double *o = coef + (t.cbase + (long)ch * spc * blk) * NA;
+        for (int e = tid; e < nslot * NA; e += 256) o[e] = buf[e];
+        __syncthreads();
+    }
+}
+
+int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx)
+{
+    const long plane = (long)li.g.nx * li.g.ny;
+    if (li.P * li.NJ > 256) return LSSP_AMD_EUNSUPPORTED;  // k_coef_refill: a step's slots within one workgroup
+    for (int upper = 0; upper < 2; upper++) {
+        LineSweep &ls = upper ? li.U : li.L;
+        if (ls.ntiles <= 0) continue;
+        const dim3 grid((unsigned)ls.ntiles, 8);
+        if (ls.NA == 4)
+            k_coef_refill<4><<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.nx, ls.ny, n, plane, ls.P, ls.LV, upper, Fp,
+                                                          Fj, Fx, ls.d_coef);
+        else
+            k_coef_refill<3><<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.nx, ls.ny, n, plane, ls.P, ls.LV, upper, Fp,
+                                                          Fj, Fx, ls.d_coef);
+    }
+    LSSP_HIP(hipGetLastError());
+    li.lstream_of = nullptr;
+    return LSSP_AMD_OK;
+}
+
 void free_line_sweep(LineILU &li)
 {
     for (LineSweep *s : {&li.L, &li.U}) {

@@ -259,6 +259,11 @@ class DMat:
         _ck(self.dev.L.lssp_amd_mat_bytes(self.h, ctypes.byref(c), ctypes.byref(a)), "mat_bytes")
         return c.value, a.value
 
+    def update_values(self, ax: DVec):
+        """New values (a device vector of nnz entries, in the handle's entry order) on the
+        same pattern: lssp_amd_mat_update_values.  Every layout is kept."""
+        _ck(self.dev.L.lssp_amd_mat_update_values(self.dev.h, self.h, ax.ptr, ax.n), "mat_update_values")
+
     def close(self):
         if self.h:
             self.dev.L.lssp_amd_mat_destroy(self.h)
@@ -361,6 +366,12 @@ class DILU:
         _ck(self.dev.L.lssp_amd_ilu_get_factors(self.h, _p(Lp), _p(Lj), _p(Lx), _p(Up), _p(Uj), _p(Ux)),
             "ilu_get_factors")
         return (Lp, Lj, Lx), (Up, Uj, Ux)
+
+    def refactor(self, A: DMat):
+        """Factor again from the values A holds now, keeping the sweep schedules
+        (lssp_amd_ilu_refactor): the tiled line-sweep ILU(0) of a 5-/7-point grid only; any
+        other handle raises LsspError with status 6 (unsupported) and stays as it was."""
+        _ck(self.dev.L.lssp_amd_ilu_refactor(self.dev.h, self.h, A.h), "ilu_refactor")
 
     def apply(self, x: DVec, rhs: DVec):
         """x = U^-1 L^-1 rhs (lssp_pc_ilu_solve, solver-tri.cxx:57-60)"""
