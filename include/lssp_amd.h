@@ -347,13 +347,17 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      bitwise the reference's.  COO in HBM -> lssp_amd_coo_to_csr ->
  *      lssp_amd_csr_sort_columns_dev -> lssp_amd_mat_from_device ->
  *      lssp_amd_solve runs without a host copy of the matrix.
- *      What still goes through the host: the ILU setup (lssp_amd_ilu_create /
- *      lssp_amd_bilu_create take host arrays, as the reference factors on the
- *      host; download the CSR for them), and the sliced copy of a windowed
- *      matrix (see lssp_amd_mat_from_device).  Both only when the PATTERN is
- *      new: new values on the same pattern stay on the device
- *      (lssp_amd_mat_update_values, and lssp_amd_ilu_refactor for the handles
- *      it serves, below). */
+ *      The tiled line-sweep ILU(0) of a natural-order 5-/7-point box is made
+ *      from the matrix handle without a host copy either
+ *      (lssp_amd_ilu_create_dev, below).
+ *      What still goes through the host: every other ILU setup
+ *      (lssp_amd_ilu_create / lssp_amd_bilu_create take host arrays, as the
+ *      reference factors on the host; download the CSR for them: ILUT, level
+ *      >= 1, block-Jacobi, BILUK, general and small 2-D factors), and the
+ *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
+ *      only when the PATTERN is new: new values on the same pattern stay on the
+ *      device (lssp_amd_mat_update_values, and lssp_amd_ilu_refactor for the
+ *      handles it serves, below). */
 /* lssp_mat_csr_is_sorted (matrix-utils.cxx:249-279): *sorted = 0 iff some row
  * holds neighbours Aj[k-1] > Aj[k] (equal neighbours are sorted); nnz == 0: 1.
  * Column values are compared only, never used as indices. */
@@ -429,6 +433,31 @@ int lssp_amd_mat_update_values(lssp_amd_ctx *ctx, lssp_amd_mat *A, const double 
  * HIP error part-way returns LSSP_AMD_EHIP, after which M may only be
  * destroyed. */
 int lssp_amd_ilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat *A);
+/* lssp_amd_ilu_create for a matrix that lives in HBM: the arguments have its
+ * meaning, the matrix is the handle's device CSR.  No matrix array is copied to
+ * the host, neither pattern nor values; a few words come back (row 0's entries,
+ * which give nx and nx * ny, and the pattern check's flag).  The handle is
+ * bitwise lssp_amd_ilu_create's of the same matrix -- applies, sweeps, solves,
+ * lssp_amd_ilu_info, lssp_amd_ilu_get_factors (the host copies of the factors
+ * are made on the first call that reads them) -- it owns copies of what it
+ * needs, so A may be destroyed, and it is made with its refactor plan:
+ * lssp_amd_ilu_refactor is eligible on it and builds nothing.
+ * Eligible: kind ILUK, level 0, one block (blk <= 0 or >= n), A single-rank and
+ * square with exactly the pattern of a complete natural-order 5-/7-point box
+ * nx x ny (x nz), nx >= 2, ny >= 8 -- column-sorted rows (run
+ * lssp_amd_csr_sort_columns_dev first when they may not be) that hold their
+ * diagonal and every grid neighbour r -+ 1, r -+ nx, r -+ nx*ny that exists --
+ * which lssp_amd_ilu_create would run on the 16 x 8 tiled line sweeps.
+ * Everything else returns LSSP_AMD_EUNSUPPORTED with *out == NULL, A and ctx
+ * untouched: ILUT, level >= 1 or < 0 (the reference's default level), block-
+ * Jacobi, an unsorted row, a missing diagonal or neighbour, a matrix that is
+ * no such box, a small 2-D grid on the one-workgroup sweeps
+ * (lssp_amd_ilu_sweep_layout *lines == ny there), LSSP_AMD_LINE=0, a distributed
+ * A; use lssp_amd_ilu_create for those.  NULL arguments, a kind that is neither
+ * ILUK nor ILUT, or nrows != ncols: LSSP_AMD_EINVAL.  A HIP error part-way:
+ * LSSP_AMD_EHIP, everything freed.  Returns when the stream has finished. */
+int lssp_amd_ilu_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p,
+                            int blk, lssp_amd_ilu **out);
 
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);

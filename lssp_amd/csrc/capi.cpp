@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10300; }
+int lssp_amd_version(void) { return 10400; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -699,6 +699,7 @@ static int sync_free_one(lssp_amd_ctx *c, int n, const std::vector<int> &Tp, con
 static int ensure_sync_free(lssp_amd_ctx *c, lssp_amd_ilu *M)
 {
     std::lock_guard<std::mutex> lk(M->sync_free_mu);
+    LSSP_TRY(refactor_host_factors(M));  // a handle made on the device has no host factors yet
     LSSP_TRY(sync_free_one(c, M->n, M->Lp, M->Lj, M->Lx, false, M->lower));
     return sync_free_one(c, M->n, M->Up, M->Uj, M->Ux, true, M->upper);
 }
@@ -846,7 +847,8 @@ int lssp_amd_ilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *
                           M->bs == 0 && li.ntiles > 0 && li.kind == 0 && li.g2 == 0 && li.P * li.NJ <= 256;
     if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
     if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
-    if ((long)A->nnz != (long)M->Lp[M->n] + M->Up[M->n] - M->n) return LSSP_AMD_EINVAL;
+    const long fnnz = M->host_missing ? (long)M->dev_nnzL + M->dev_nnzU - M->n : (long)M->Lp[M->n] + M->Up[M->n] - M->n;
+    if ((long)A->nnz != fnnz) return LSSP_AMD_EINVAL;
     // LSSP_AMD_SETUP_TIMES=1: the phases' own durations (the stream drained after each)
     static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
     try {
@@ -878,6 +880,104 @@ int lssp_amd_ilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *
         return LSSP_AMD_ENOMEM;
     }
     return LSSP_AMD_OK;
+}
+
+// lssp_amd_ilu_create for a box matrix in HBM: what ilu_create builds on the
+// host from the factors is built here from the grid (tiles, layouts, buffers:
+// build_line_sweep_box) and on the device from the matrix (pattern check, level
+// lists in closed form, k_ilu0_level, k_coef_refill).  The handle is born with
+// its refactor plan; its host factor copies wait for a reader.
+static int ilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int level, int blk, lssp_amd_ilu **out)
+{
+    const int n = A->nrows, nnz = A->nnz;
+    if (kind != LSSP_AMD_ILUK || level != 0 || !(blk <= 0 || blk >= n) || A->dist || A->nhalo > 0)
+        return LSSP_AMD_EUNSUPPORTED;
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    LSSP_HIP(hipSetDevice(c->device));
+    const double t_start = wall_time();
+    double t0 = t_start;
+    auto mark = [&](const char *phase) -> int {  // LSSP_AMD_SETUP_TIMES=1: the phases' own durations, the stream drained
+        if (!times) return LSSP_AMD_OK;
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        const double t = wall_time();
+        fprintf(stderr, "lssp_amd create_dev: %-22s %10.6f s\n", phase, t - t0);
+        t0 = t;
+        return LSSP_AMD_OK;
+    };
+    // geometry: row 0 of a box holds {0, 1, nx, nx * ny} (2-D: {0, 1, nx})
+    if (nnz < 3) return LSSP_AMD_EUNSUPPORTED;
+    int h_p[2] = {0, 0}, h_j[4] = {0, 0, 0, 0};
+    LSSP_HIP(hipMemcpyAsync(h_p, A->Ap, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h_j, A->Aj, sizeof(int) * std::min(nnz, 4), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    const int len0 = h_p[1] - h_p[0];
+    if (h_p[0] != 0 || (len0 != 3 && len0 != 4) || len0 > nnz || h_j[0] != 0 || h_j[1] != 1)
+        return LSSP_AMD_EUNSUPPORTED;
+    const long nx = h_j[2], plane = len0 == 4 ? (long)h_j[3] : (long)n;
+    if (nx < 2 || plane < nx || plane % nx || n % plane) return LSSP_AMD_EUNSUPPORTED;
+    const long ny = plane / nx, nz = n / plane;
+    if ((len0 == 4) != (nz > 1)) return LSSP_AMD_EUNSUPPORTED;
+    const long strict = (nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1);  // on each side of the diagonal
+    if (2 * strict + n != (long)nnz) return LSSP_AMD_EUNSUPPORTED;
+    if (!line_box_tiled((int)nx, (int)ny, (int)nz)) return LSSP_AMD_EUNSUPPORTED;
+    int ok = 0;
+    LSSP_TRY(box_pattern_check(c, n, nnz, A->Ap, A->Aj, (int)nx, (int)ny, (int)nz, &ok));
+    if (!ok) return LSSP_AMD_EUNSUPPORTED;
+    LSSP_TRY(mark("pattern check"));
+
+    lssp_amd_ilu *M = new lssp_amd_ilu();
+    M->ctx = c;
+    M->n = n;
+    M->c_kind = kind;
+    M->c_level = level;
+    M->c_blk = blk;
+    auto build = [&]() -> int {
+        LSSP_TRY(refactor_plan_from_box(c, n, nnz, A->Ap, A->Aj, (int)nx, (int)ny, (int)nz, &M->rf));
+        LSSP_TRY(mark("plan / levels"));
+        LSSP_TRY(refactor_numeric(c, *M->rf, n, A->Ax));
+        LSSP_TRY(mark("numeric ILU(0)"));
+        LSSP_TRY(build_line_sweep_box(c, (int)nx, (int)ny, (int)nz, M->line));
+        LSSP_TRY(mark("allocation + zeroing"));
+        LSSP_TRY(launch_line_refill(c, M->line, n, M->rf->d_Fp, M->rf->d_Fj, M->rf->d_Fx));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        LSSP_TRY(mark("coefficient streams"));
+        return LSSP_AMD_OK;
+    };
+    int st;
+    try {
+        st = build();
+    } catch (const std::exception &) {
+        st = LSSP_AMD_ENOMEM;
+    }
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        lssp_amd_ilu_destroy(M);
+        return st;
+    }
+    // what ilu_upload's level passes report: row (i, j, k) is on level i + j + k of
+    // L's DAG and on the mirrored level of U's
+    M->lower.n = M->upper.n = n;
+    M->lower.nlevels = M->upper.nlevels = (int)(nx + ny + nz - 2);
+    M->host_missing = M->host_stale = true;
+    M->dev_nnzL = M->dev_nnzU = (int)(strict + n);
+    M->setup_seconds = wall_time() - t_start;
+    *out = M;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_ilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int level, double tol, int p, int blk,
+                            lssp_amd_ilu **out)
+{
+    (void)tol;  // ILUT's arguments: accepted as lssp_amd_ilu_create takes them, ILUT itself is not made here
+    (void)p;
+    if (out) *out = nullptr;
+    if (!c || !A || !out || A->nrows <= 0 || A->nrows != A->ncols || (kind != LSSP_AMD_ILUK && kind != LSSP_AMD_ILUT))
+        return LSSP_AMD_EINVAL;
+    try {
+        return ilu_create_dev(c, A, kind, level, blk, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
 }
 
 static int ilu_from_factors(lssp_amd_ctx *c, int n, const int *Lp, const int *Lj, const double *Lx, const int *Up,
@@ -1158,8 +1258,8 @@ int lssp_amd_ilu_info(const lssp_amd_ilu *M, int *n, int *nnzL, int *nnzU, int *
 {
     if (!M) return LSSP_AMD_EINVAL;
     if (n) *n = M->n;
-    if (nnzL) *nnzL = (int)M->Lj.size();
-    if (nnzU) *nnzU = (int)M->Uj.size();
+    if (nnzL) *nnzL = M->host_missing ? M->dev_nnzL : (int)M->Lj.size();
+    if (nnzU) *nnzU = M->host_missing ? M->dev_nnzU : (int)M->Uj.size();
     if (levelsL) *levelsL = M->lower.nlevels;
     if (levelsU) *levelsU = M->upper.nlevels;
     if (setup_seconds) *setup_seconds = M->setup_seconds;
@@ -1180,8 +1280,9 @@ int lssp_amd_ilu_get_factors(const lssp_amd_ilu *M, int *Lp, int *Lj, double *Lx
                              double *Ux)
 {
     if (!M) return LSSP_AMD_EINVAL;
-    // after lssp_amd_ilu_refactor the host copies of the values are brought up to date here
-    if (Lx || Ux) LSSP_TRY(refactor_host_factors(const_cast<lssp_amd_ilu *>(M)));
+    // after lssp_amd_ilu_refactor the host copies of the values are brought up to date here;
+    // a handle made by lssp_amd_ilu_create_dev gets its host copies here
+    if (Lx || Ux || M->host_missing) LSSP_TRY(refactor_host_factors(const_cast<lssp_amd_ilu *>(M)));
     if (Lp) memcpy(Lp, M->Lp.data(), sizeof(int) * M->Lp.size());
     if (Lj) memcpy(Lj, M->Lj.data(), sizeof(int) * M->Lj.size());
     if (Lx) memcpy(Lx, M->Lx.data(), sizeof(double) * M->Lx.size());

@@ -207,6 +207,143 @@ int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M)
     return LSSP_AMD_OK;
 }
 
+// ---------------------------------------------------------------------------
+// lssp_amd_ilu_create_dev: the plan of a complete box without a host pass
+// ---------------------------------------------------------------------------
+// One thread per row, grid-strided: row r = (i, j, k) of the nx x ny x nz box
+// must hold exactly {r - plane, r - nx, r - 1, r, r + 1, r + nx, r + plane},
+// each where its neighbour exists, in that (ascending) order.  Ap is not
+// trusted: a row is read only when its range lies inside [0, nnz) and has the
+// expected length.  Any mismatch ORs *flag.
+__global__ __launch_bounds__(256) void k_box_check(int n, int nnz, int nx, int ny, int nz, const int *__restrict__ Ap,
+                                                   const int *__restrict__ Aj, int *__restrict__ flag)
+{
+    const long plane = (long)nx * ny;
+    bool bad = false;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256) {
+        const int i = (int)(r % nx);
+        const long q = r / nx;
+        const int j = (int)(q % ny), k = (int)(q / ny);
+        const bool km = k > 0, jm = j > 0, im = i > 0, ip = i < nx - 1, jp = j < ny - 1, kp = k < nz - 1;
+        const int len = 1 + km + jm + im + ip + jp + kp;
+        const int a = Ap[r], b = Ap[r + 1];
+        if (r == 0) bad |= a != 0;
+        if (r == n - 1) bad |= b != nnz;
+        if (a < 0 || b > nnz || b < a || b - a != len) {
+            bad = true;
+            continue;
+        }
+        int e = a;
+        if (km) bad |= (long)Aj[e++] != r - plane;
+        if (jm) bad |= (long)Aj[e++] != r - nx;
+        if (im) bad |= (long)Aj[e++] != r - 1;
+        bad |= (long)Aj[e++] != r;
+        if (ip) bad |= (long)Aj[e++] != r + 1;
+        if (jp) bad |= (long)Aj[e++] != r + nx;
+        if (kp) bad |= (long)Aj[e++] != r + plane;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+int box_pattern_check(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int nx, int ny, int nz, int *ok)
+{
+    *ok = 0;
+    if ((long)nx * ny * nz != (long)n) return LSSP_AMD_OK;
+    int *d_flag = nullptr;
+    LSSP_HIP(hipMalloc(&d_flag, sizeof(int)));
+    auto run = [&]() -> int {
+        LSSP_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
+        k_box_check<<<(unsigned)std::min<long>(((long)n + 255) / 256, 16384), 256, 0, c->stream>>>(n, nnz, nx, ny, nz,
+                                                                                                 dAp, dAj, d_flag);
+        LSSP_HIP(hipGetLastError());
+        int bad = 1;
+        LSSP_HIP(hipMemcpyAsync(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        *ok = !bad;
+        return LSSP_AMD_OK;
+    };
+    const int st = run();
+    (void)hipFree(d_flag);
+    return st;
+}
+
+// d_rows of a complete box in closed form.  Row (i, j, k) has level l = i + j +
+// k; inside a level rows ascend, i.e. by k, then j.  With c2(m) = the number of
+// (i, j) of the nx x ny plane on i + j = m and C2 its running sum (C2[x] = sum
+// of c2(m), m < x), the rows of level l before (i, j, k) are the planes k' < k,
+// c2(l - k') each = C2[l + 1] - C2[l - k + 1], and on plane k the lines j' < j
+// that reach the diagonal m = i + j: j - max(0, m - nx + 1).  tab = C2[0 ..
+// nlev], then lev_off[0 .. nlev].  A position outside [0, n) (never, on a box)
+// is dropped and ORs *flag.
+__global__ __launch_bounds__(256) void k_box_levels(int n, int nx, int ny, int nlev, const int *__restrict__ tab,
+                                                    int *__restrict__ rows, int *__restrict__ flag)
+{
+    const int *C2 = tab, *off = tab + nlev + 1;
+    bool bad = false;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256) {
+        const int i = (int)(r % nx);
+        const long q = r / nx;
+        const int j = (int)(q % ny), k = (int)(q / ny);
+        const int m = i + j, l = m + k;
+        const long pos = (long)off[l] + (C2[l + 1] - C2[m + 1]) + (j - max(0, m - nx + 1));
+        if (pos < 0 || pos >= n) bad = true;
+        else rows[pos] = (int)r;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+int refactor_plan_from_box(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int nx, int ny, int nz,
+                           RefactorPlan **out)
+{
+    *out = nullptr;
+    if ((long)nx * ny * nz != (long)n || nnz < n) return LSSP_AMD_EINVAL;
+    const int nlev = nx + ny + nz - 2;
+    // the two tables from the grid alone (no pass over the matrix)
+    std::vector<int> tab(2 * (size_t)nlev + 2);
+    int *C2 = tab.data(), *off = tab.data() + nlev + 1;
+    C2[0] = 0;
+    for (int m = 0; m < nlev; m++) {
+        const int c2 = m <= nx + ny - 2 ? std::min(std::min(m, nx + ny - 2 - m), std::min(nx, ny) - 1) + 1 : 0;
+        C2[m + 1] = C2[m] + c2;
+    }
+    off[0] = 0;
+    for (int l = 0; l < nlev; l++) off[l + 1] = off[l] + (C2[l + 1] - C2[std::max(l - nz + 1, 0)]);
+    if (off[nlev] != n) return LSSP_AMD_EINVAL;
+    RefactorPlan *p = new RefactorPlan();
+    p->nnz = nnz;
+    p->lev_off.assign(off, off + nlev + 1);
+    int *d_tab = nullptr;
+    auto fill = [&]() -> int {
+        LSSP_HIP(hipMalloc(&p->d_Fp, sizeof(int) * ((size_t)n + 1)));
+        LSSP_HIP(hipMalloc(&p->d_Fj, sizeof(int) * (size_t)nnz));
+        LSSP_HIP(hipMalloc(&p->d_Fx, sizeof(double) * (size_t)nnz));
+        LSSP_HIP(hipMalloc(&p->d_dinv, sizeof(double) * (size_t)n));
+        LSSP_HIP(hipMalloc(&p->d_rows, sizeof(int) * (size_t)n));
+        LSSP_HIP(hipMalloc(&p->d_flag, sizeof(int)));
+        LSSP_HIP(hipMalloc(&d_tab, sizeof(int) * tab.size()));
+        LSSP_HIP(hipMemcpy(d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+        LSSP_HIP(hipMemcpyAsync(p->d_Fp, dAp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice, c->stream));
+        LSSP_HIP(hipMemcpyAsync(p->d_Fj, dAj, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToDevice, c->stream));
+        LSSP_HIP(hipMemsetAsync(p->d_flag, 0, sizeof(int), c->stream));
+        k_box_levels<<<(unsigned)std::min<long>(((long)n + 255) / 256, 16384), 256, 0, c->stream>>>(n, nx, ny, nlev, d_tab,
+                                                                                                  p->d_rows, p->d_flag);
+        LSSP_HIP(hipGetLastError());
+        int bad = 1;
+        LSSP_HIP(hipMemcpyAsync(&bad, p->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        return bad ? LSSP_AMD_EINVAL : LSSP_AMD_OK;
+    };
+    const int st = fill();
+    if (d_tab) (void)hipFree(d_tab);
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        refactor_plan_free(p);
+        return st;
+    }
+    *out = p;
+    return LSSP_AMD_OK;
+}
+
 int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same)
 {
     LSSP_HIP(hipMemsetAsync(p.d_flag, 0, sizeof(int), c->stream));
@@ -241,6 +378,39 @@ int refactor_host_factors(lssp_amd_ilu *M)
     if (!M->host_stale || !M->rf) return LSSP_AMD_OK;
     lssp_amd_ctx *c = M->ctx;
     const int n = M->n;
+    if (M->host_missing) {
+        // a handle made by lssp_amd_ilu_create_dev: the patterns first, split from
+        // the device F as ilu_factor splits them (row i of L: the columns below i,
+        // then the unit diagonal; of U: the pivot, then the columns above i)
+        std::vector<int> Fp((size_t)n + 1), Fj((size_t)M->rf->nnz);
+        LSSP_HIP(hipMemcpyAsync(Fp.data(), M->rf->d_Fp, sizeof(int) * Fp.size(), hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Fj.data(), M->rf->d_Fj, sizeof(int) * Fj.size(), hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        std::vector<int> Lp((size_t)n + 1), Up((size_t)n + 1);
+        Lp[0] = Up[0] = 0;
+        for (int i = 0; i < n; i++) {
+            int nl = 0;
+            while (Fp[i] + nl < Fp[i + 1] && Fj[Fp[i] + nl] < i) nl++;
+            Lp[i + 1] = Lp[i] + nl + 1;
+            Up[i + 1] = Up[i] + (Fp[i + 1] - Fp[i] - nl);
+        }
+        std::vector<int> Lj((size_t)Lp[n]), Uj((size_t)Up[n]);
+        parallel_for(n, [&](long i0, long i1) {
+            for (long i = i0; i < i1; i++) {
+                const int nl = Lp[i + 1] - Lp[i] - 1, nu = Up[i + 1] - Up[i];
+                for (int q = 0; q < nl; q++) Lj[Lp[i] + q] = Fj[Fp[i] + q];
+                Lj[Lp[i + 1] - 1] = (int)i;
+                for (int q = 0; q < nu; q++) Uj[Up[i] + q] = Fj[Fp[i] + nl + q];
+            }
+        });
+        M->Lx.assign(Lj.size(), 0.0);
+        M->Ux.assign(Uj.size(), 0.0);
+        M->Lp = std::move(Lp);
+        M->Lj = std::move(Lj);
+        M->Up = std::move(Up);
+        M->Uj = std::move(Uj);
+        M->host_missing = false;
+    }
     std::vector<double> Fx((size_t)M->rf->nnz);
     LSSP_HIP(hipMemcpyAsync(Fx.data(), M->rf->d_Fx, sizeof(double) * Fx.size(), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));

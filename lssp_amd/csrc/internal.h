@@ -289,6 +289,11 @@ struct lssp_amd_ilu {
     int c_kind = 0, c_level = 0, c_blk = 0;
     lssp_amd::RefactorPlan *rf = nullptr;  // built by the first lssp_amd_ilu_refactor
     bool host_stale = false;  // Lx / Ux are older than the device factors (refreshed by get_factors)
+    // made by lssp_amd_ilu_create_dev: the host copies Lp .. Ux do not exist until
+    // something reads them (refactor_host_factors splits them from the device F);
+    // until then the entry counts are these
+    bool host_missing = false;
+    int dev_nnzL = 0, dev_nnzU = 0;
 };
 
 namespace lssp_amd {
@@ -444,6 +449,13 @@ int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const s
                      const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
                      const std::vector<double> &Ux, LineILU &li);
 int line_rearm(lssp_amd_ctx *c, LineILU &li);
+// lssp_amd_ilu_create_dev: the tiled sweeps of the ILU(0) of a complete nx x ny
+// x nz box from the grid alone -- build_line_sweep's tiles, layouts and buffers,
+// the coefficient streams zeroed for launch_line_refill.  line_box_tiled:
+// build_line_sweep would put that factor on the 16 x 8 tiles (not on the
+// one-workgroup route, not switched off); else EUNSUPPORTED.
+bool line_box_tiled(int nx, int ny, int nz);
+int build_line_sweep_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li);
 // linefill.hip: the 7-point ILU(1) pattern (EUNSUPPORTED when the factor is not it)
 int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
                    const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
@@ -475,6 +487,17 @@ void refactor_plan_free(RefactorPlan *p);
 int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same);
 int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx);
 int refactor_host_factors(lssp_amd_ilu *M);
+// lssp_amd_ilu_create_dev (ilu_factor.hip), for a device CSR (n rows, nnz
+// entries) and a box nx x ny x nz = n.  box_pattern_check: *ok = the pattern is
+// exactly the complete natural-order 5-/7-point stencil of that box, rows
+// column-sorted (one flag word read back).  refactor_plan_from_box: the plan of
+// such a matrix without a host pass over it -- F's pattern copied device to
+// device, the level lists in closed form (row (i, j, k) has level i + j + k;
+// rows ascending inside a level, as level_lists orders them).
+int box_pattern_check(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int nx, int ny, int nz,
+                      int *ok);
+int refactor_plan_from_box(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int nx, int ny, int nz,
+                           RefactorPlan **out);
 // linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
 // the factored values Fx on the pattern (Fp, Fj); every slot is written
 int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);

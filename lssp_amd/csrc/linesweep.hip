@@ -212,10 +212,15 @@ static int build_tiles(const LineGeom &g, int P, int NJ, int LV, int W, std::vec
 // rows (row (p, l) at p*nj + l; rows not valid at that step are +0.0), each
 // row's NA coefficients {c_k, c_j, c_i(, diag)} together.  Fixed strides keep
 // every role's addressing to a per-lane base plus immediate offsets.
-static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, const CoefSrc &src,
-                        int NA, LineSweep &ls)
+// + slack for the loaders' whole 1 KB pieces past the last block
+static inline size_t coef_len(const LineSweep &ls) { return (size_t)ls.rows_total * ls.NA + 16 * 1024 / 8; }
+
+// The part that depends on the grid alone: every tile's place in the streams,
+// the tile table, the claim counter and order, and the coefficient stream's
+// allocation (its values: upload_sweep from host factors, or k_coef_refill).
+static int layout_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, int NA, LineSweep &ls)
 {
-    const int nx = g.nx, P = ls.P, LV = ls.LV;
+    const int P = ls.P, LV = ls.LV;
     std::vector<LineTile> tt = tiles;
     long rows_total = 0;
     int tmax = 0;
@@ -225,27 +230,6 @@ static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<Li
         rows_total += (long)t.T * P * t.nj;
         tmax = std::max(tmax, t.T);
     }
-    // + slack for the loaders' whole 1 KB pieces past the last block
-    const long slack = 16 * 1024 / 8;
-    std::vector<double> coef((size_t)rows_total * NA + slack, 0.0);
-    parallel_for((long)tt.size(), [&](long t0, long t1) {
-    for (long ti = t0; ti < t1; ti++) {
-        const LineTile &t = tt[ti];
-        for (int s = 0; s < t.T; s++) {
-            double *blk = coef.data() + (size_t)(t.cbase + (long)s * P * t.nj) * NA;
-            for (int p = 0; p < t.np; p++) {
-                int lo, hi;
-                const int sg = line_sigma(LV, P, p);
-                step_range(nx, t.nj, t.np, s, p, sg, lo, hi);
-                for (int l = lo; l <= hi; l++) {
-                    const long i = s - l - p - sg;
-                    const long r = ((long)(t.k0 + p) * g.ny + (t.j0 + l)) * nx + i;
-                    for (int a = 0; a < NA; a++) blk[(size_t)(p * t.nj + l) * NA + a] = src.get(r, a);
-                }
-            }
-        }
-    }
-    });
     ls.nx = g.nx;
     ls.ny = g.ny;
     ls.nz = g.nz;
@@ -255,8 +239,7 @@ static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<Li
     ls.NA = NA;
     LSSP_HIP(hipMalloc(&ls.d_tiles, sizeof(LineTile) * tt.size()));
     LSSP_HIP(hipMemcpy(ls.d_tiles, tt.data(), sizeof(LineTile) * tt.size(), hipMemcpyHostToDevice));
-    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * coef.size()));
-    LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
+    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * coef_len(ls)));
     LSSP_HIP(hipMalloc(&ls.d_claim, sizeof(unsigned long long)));
     LSSP_HIP(hipMemset(ls.d_claim, 0, sizeof(unsigned long long)));
     if (LV >= 2) {
@@ -276,6 +259,36 @@ static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<Li
         LSSP_HIP(hipMemcpy(ls.d_order, ord.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
     }
     ls.h_tiles = std::move(tt);
+    (void)c;
+    return LSSP_AMD_OK;
+}
+
+// the coefficient stream of a laid-out sweep from the host factors
+static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc &src, LineSweep &ls)
+{
+    const int nx = g.nx, P = ls.P, LV = ls.LV, NA = ls.NA;
+    const std::vector<LineTile> &tt = ls.h_tiles;
+    std::vector<double> coef(coef_len(ls), 0.0);
+    parallel_for((long)tt.size(), [&](long t0, long t1) {
+    for (long ti = t0; ti < t1; ti++) {
+        const LineTile &t = tt[ti];
+        for (int s = 0; s < t.T; s++) {
+            double *blk = coef.data() + (size_t)(t.cbase + (long)s * P * t.nj) * NA;
+            for (int p = 0; p < t.np; p++) {
+                int lo, hi;
+                const int sg = line_sigma(LV, P, p);
+                step_range(nx, t.nj, t.np, s, p, sg, lo, hi);
+                for (int l = lo; l <= hi; l++) {
+                    const long i = s - l - p - sg;
+                    const long r = ((long)(t.k0 + p) * g.ny + (t.j0 + l)) * nx + i;
+                    for (int a = 0; a < NA; a++) blk[(size_t)(p * t.nj + l) * NA + a] = src.get(r, a);
+                }
+            }
+        }
+    }
+    });
+    LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
+    (void)c;
     return LSSP_AMD_OK;
 }
 
@@ -292,33 +305,28 @@ static void line_plan(const LineGeom &, int &P, int &NJ, int &LV)
     LV = 2;  // levels per workgroup step (4 measured slower)
 }
 
-int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
-                     const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
-                     const std::vector<double> &Ux, LineILU &li)
+// the two switches of the tiled route: LSSP_AMD_LINE=0 turns the line sweeps
+// off; a small 2-D grid (exam.cxx's 5-point Poisson) runs on one workgroup,
+// lines on lanes (linefill.hip k_lineg), unless LSSP_AMD_LINEG=0 keeps the tiles
+static bool line_enabled()
 {
     const char *env = getenv("LSSP_AMD_LINE");
-    if (env && !atoi(env)) return LSSP_AMD_EUNSUPPORTED;
-    LineGeom g;
-    if (!detect_grid(n, Lp, Lj, Lx, Up, Uj, g)) return build_linefill(c, n, Lp, Lj, Lx, Up, Uj, Ux, li);
-    {
-        // a small 2-D grid (exam.cxx's 5-point Poisson): one workgroup, lines on
-        // lanes (linefill.hip k_lineg); LSSP_AMD_LINEG=0 keeps the tiles
-        const char *e = getenv("LSSP_AMD_LINEG");
-        if (g.nz == 1 && g.ny <= G2_MAXNY && lineg_fits(g, 0) && !(e && !atoi(e))) {
-            const long plane = (long)g.nx * g.ny;
-            const int ncl = g.unitL ? 2 : 3;
-            CoefSrc sl, su;
-            sl.build(Lp, Lj, Lx, false, n, g.nx, plane, g.unitL ? 3 : 4);
-            su.build(Up, Uj, Ux, true, n, g.nx, plane, 4);
-            // k_lineg's components: S, W (, diag) = CoefSrc's 1, 2 (, 3)
-            std::vector<double> cl((size_t)n * ncl), cu((size_t)n * 3);
-            for (long r = 0; r < n; r++) {
-                for (int k = 0; k < ncl; k++) cl[r * ncl + k] = sl.get(r, 1 + k);
-                for (int k = 0; k < 3; k++) cu[r * 3 + k] = su.get(r, 1 + k);
-            }
-            return build_lineg(c, g, 0, ncl, cl, cu, li);
-        }
-    }
+    return !(env && !atoi(env));
+}
+static bool lineg_route(const LineGeom &g)
+{
+    const char *e = getenv("LSSP_AMD_LINEG");
+    return g.nz == 1 && g.ny <= G2_MAXNY && lineg_fits(g, 0) && !(e && !atoi(e));
+}
+
+// Everything of the tiled k_line2 sweeps that the grid alone decides: the L
+// tiles and their mirrored U tiles, both stream layouts, claim counters and
+// order, the rhs streams (zeroed) and the armed hand-off buffers.  The
+// coefficient streams are allocated here; cl / cu (host factors) fill them, or,
+// both nullptr, they are zeroed on the context's stream for
+// launch_line_refill to write.
+static int build_line_tiles(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc *cl, const CoefSrc *cu, LineILU &li)
+{
     int P, NJ, LV;
     line_plan(g, P, NJ, LV);
     const int W = (g.ny + NJ - 1) / NJ;
@@ -342,23 +350,26 @@ int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const s
             u.tk = kin ? (Kp - 1) * W + Jp : -1;
             u.tj = Jp > 0 ? Kp * W + Jp - 1 : -1;
         }
-    const long plane = (long)g.nx * g.ny;
     // coefficients per row: c_k, c_j, c_i (unit L), + diag
     const int NAD = 4;
     const int NAL = g.unitL ? 3 : NAD;
-    CoefSrc cl, cu;
-    cl.build(Lp, Lj, Lx, false, n, g.nx, plane, NAL);
-    cu.build(Up, Uj, Ux, true, n, g.nx, plane, NAD);
     li.g = g;
     li.P = li.L.P = li.U.P = P;
     li.NJ = li.L.NJ = li.U.NJ = NJ;
     li.LV = li.L.LV = li.U.LV = LV;
     li.W = W;
     li.S = S;
-    LSSP_TRY(upload_sweep(c, g, Lt, cl, NAL, li.L));
+    LSSP_TRY(layout_sweep(c, g, Lt, NAL, li.L));
     LineGeom gu = g;
     for (int k = 0; k < g.nz; k++) gu.kin[k] = k > 0 ? g.kin[g.nz - k] : 0;
-    LSSP_TRY(upload_sweep(c, gu, Ut, cu, NAD, li.U));
+    LSSP_TRY(layout_sweep(c, gu, Ut, NAD, li.U));
+    if (cl && cu) {
+        LSSP_TRY(upload_sweep(c, g, *cl, li.L));
+        LSSP_TRY(upload_sweep(c, gu, *cu, li.U));
+    } else {
+        LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * coef_len(li.L), c->stream));
+        LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * coef_len(li.U), c->stream));
+    }
     // the L sweep writes its output into the U sweep's rhs stream: per L tile
     // the base row of its mirror U tile
     for (int K = 0; K < S; K++)
@@ -387,6 +398,61 @@ int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const s
     LSSP_TRY(line_rearm(c, li));
     LSSP_HIP(hipStreamSynchronize(c->stream));
     return LSSP_AMD_OK;
+}
+
+int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
+                     const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
+                     const std::vector<double> &Ux, LineILU &li)
+{
+    if (!line_enabled()) return LSSP_AMD_EUNSUPPORTED;
+    LineGeom g;
+    if (!detect_grid(n, Lp, Lj, Lx, Up, Uj, g)) return build_linefill(c, n, Lp, Lj, Lx, Up, Uj, Ux, li);
+    if (lineg_route(g)) {
+        const long plane = (long)g.nx * g.ny;
+        const int ncl = g.unitL ? 2 : 3;
+        CoefSrc sl, su;
+        sl.build(Lp, Lj, Lx, false, n, g.nx, plane, g.unitL ? 3 : 4);
+        su.build(Up, Uj, Ux, true, n, g.nx, plane, 4);
+        // k_lineg's components: S, W (, diag) = CoefSrc's 1, 2 (, 3)
+        std::vector<double> cl((size_t)n * ncl), cu((size_t)n * 3);
+        for (long r = 0; r < n; r++) {
+            for (int k = 0; k < ncl; k++) cl[r * ncl + k] = sl.get(r, 1 + k);
+            for (int k = 0; k < 3; k++) cu[r * 3 + k] = su.get(r, 1 + k);
+        }
+        return build_lineg(c, g, 0, ncl, cl, cu, li);
+    }
+    const long plane = (long)g.nx * g.ny;
+    CoefSrc cl, cu;
+    cl.build(Lp, Lj, Lx, false, n, g.nx, plane, g.unitL ? 3 : 4);
+    cu.build(Up, Uj, Ux, true, n, g.nx, plane, 4);
+    return build_line_tiles(c, g, &cl, &cu, li);
+}
+
+// lssp_amd_ilu_create_dev: the ILU(0) of a complete nx x ny x nz box (unit L,
+// every plane joined to the one below it)
+static bool box_geom(int nx, int ny, int nz, LineGeom &g)
+{
+    if (nx < 2 || ny < 8 || nz < 1) return false;  // detect_grid's limits
+    g.nx = nx;
+    g.ny = ny;
+    g.nz = nz;
+    g.kin.assign(nz, 1);
+    g.kin[0] = 0;
+    g.unitL = true;
+    return true;
+}
+// build_line_sweep would put that factor on the 16 x 8 tiles
+bool line_box_tiled(int nx, int ny, int nz)
+{
+    LineGeom g;
+    return line_enabled() && box_geom(nx, ny, nz, g) && !lineg_route(g);
+}
+// its tiled sweeps, coefficient streams zeroed (launch_line_refill writes them)
+int build_line_sweep_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li)
+{
+    LineGeom g;
+    if (!line_box_tiled(nx, ny, nz) || !box_geom(nx, ny, nz, g)) return LSSP_AMD_EUNSUPPORTED;
+    return build_line_tiles(c, g, nullptr, nullptr, li);
 }
 
 int line_rearm(lssp_amd_ctx *c, LineILU &li)

@@ -319,6 +319,17 @@ class DILU:
         return cls(dev, h)
 
     @classmethod
+    def create_dev(cls, dev: Device, A: DMat, kind=ILUK, level=0, tol=1e-3, p=-1, blk=0):
+        """create() for a matrix that lives in HBM (lssp_amd_ilu_create_dev): the tiled
+        line-sweep ILU(0) of a natural-order 5-/7-point box, built on the device from A's
+        arrays and bitwise create()'s handle; refactor() is eligible on it at once.  Rows must
+        be column-sorted.  Anything else raises LsspError with status 6 (unsupported) and
+        leaves A as it was: use create() there."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_ilu_create_dev(dev.h, A.h, kind, level, tol, p, blk, ctypes.byref(h)), "ilu_create_dev")
+        return cls(dev, h)
+
+    @classmethod
     def from_factors(cls, dev: Device, L, U):
         Lp, Lj, Lx = _i32(L[0]), _i32(L[1]), _f64(L[2])
         Up, Uj, Ux = _i32(U[0]), _i32(U[1]), _f64(U[2])
