@@ -356,8 +356,9 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      >= 1, block-Jacobi, BILUK, general and small 2-D factors), and the
  *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
  *      only when the PATTERN is new: new values on the same pattern stay on the
- *      device (lssp_amd_mat_update_values, and lssp_amd_ilu_refactor for the
- *      handles it serves, below). */
+ *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor for the
+ *      handles it serves and lssp_amd_bilu_refactor for packet-swept BILUK
+ *      handles, below). */
 /* lssp_mat_csr_is_sorted (matrix-utils.cxx:249-279): *sorted = 0 iff some row
  * holds neighbours Aj[k-1] > Aj[k] (equal neighbours are sorted); nnz == 0: 1.
  * Column values are compared only, never used as indices. */
@@ -433,6 +434,42 @@ int lssp_amd_mat_update_values(lssp_amd_ctx *ctx, lssp_amd_mat *A, const double 
  * HIP error part-way returns LSSP_AMD_EHIP, after which M may only be
  * destroyed. */
 int lssp_amd_ilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat *A);
+/* The same for a BILUK handle: factor M again from the values A holds now, on
+ * the block pattern M was created with.  Every schedule is kept and no matrix
+ * or factor array crosses the host (two flag words are read back).  Afterwards
+ * lssp_amd_ilu_apply / _apply_async + _check / _trisolve / lssp_amd_solve with M,
+ * lssp_amd_ilu_get_factors and lssp_amd_ilu_get_diag are bitwise those of a
+ * fresh lssp_amd_bilu_create(A's arrays, M's level, M's bs) -- hence of
+ * lssp_amd_bilu_factor_host on the new values; lssp_amd_ilu_info and
+ * _sweep_layout answer as before.  The host copies of L, U and the inverses
+ * are refreshed by the next call that reads them (one download), and the
+ * arrays a single sweep (lssp_amd_ilu_trisolve) built are dropped and rebuilt
+ * by the next one.  All work is enqueued on the context's stream, after any
+ * earlier lssp_amd_ilu_apply_async; the call returns when the stream has
+ * finished.
+ * Eligible: M from lssp_amd_bilu_create with bs <= 8 (the device numeric path)
+ * whose two sweeps run on packet schedules.  An ILUK / ILUT handle, a handle
+ * from lssp_amd_ilu_from_ldu / _from_factors, bs 9..32, a handle on the
+ * sync-free fallback (a factor row longer than 24 entries) and a distributed A
+ * return LSSP_AMD_EUNSUPPORTED with M unchanged and usable.
+ * Pattern rule: A is n x n with M's n and has the BLOCK graph M was created
+ * from -- every entry of A lies in a block the creating matrix had, and every
+ * block the creating matrix had holds at least one entry of A.  The symbolic
+ * pattern at M's level is then M's.  Inside blocks the scalar pattern is free:
+ * A's nnz may differ, absent entries are 0.0, columns need not be sorted, and
+ * of a duplicated column the last occurrence in storage order counts.  Checked
+ * on the device (columns outside [0, n) included); a violation or another n
+ * returns LSSP_AMD_EINVAL, as does an exactly singular diagonal block, with M
+ * unchanged in both cases: the handle's record streams and inverses are
+ * written last, after both flags are read.  NULL arguments: LSSP_AMD_EINVAL.
+ * The first call builds a plan kept until lssp_amd_ilu_destroy: the block
+ * pattern with each block's row and graph flag, the hit marks, two block value
+ * buffers (scratch, and the committed values the refill and the host refresh
+ * read), the scratch inverses and the level lists of the block rows --
+ * 16 bs^2 + 10 B per block and 8 bs^2 + 12 B per block row of device memory;
+ * a handle that is never refactored allocates none of it.  A HIP error
+ * part-way returns LSSP_AMD_EHIP, after which M may only be destroyed. */
+int lssp_amd_bilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat *A);
 /* lssp_amd_ilu_create for a matrix that lives in HBM: the arguments have its
  * meaning, the matrix is the handle's device CSR.  No matrix array is copied to
  * the host, neither pattern nor values; a few words come back (row 0's entries,

@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10400; }
+int lssp_amd_version(void) { return 10500; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -1010,15 +1010,16 @@ static int ilu_from_factors(lssp_amd_ctx *c, int n, const int *Lp, const int *Lj
 // ---- BILUK (pc-biluk.cxx) --------------------------------------------------------
 // steps 1-4 of the setup on the host copy A; c != nullptr and bs <= 8: the
 // numeric block ILU(0) on c's GPU (bilu_factor.hip), else on the host
+// T: the factored BCSR (its pattern is what lssp_amd_bilu_refactor keeps); *level_out: the level used
 static int bilu_factor(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, const double *Ax, int level, int bs,
-                       HostCSR &L, HostCSR &U, std::vector<double> &inv)
+                       HostCSR &L, HostCSR &U, std::vector<double> &inv, HostBCSR &T, int *level_out = nullptr)
 {
     if (n <= 0 || !Ap || !Aj || !Ax || bs < 1 || bs > BILU_MAX_BS || n % bs != 0) return LSSP_AMD_EINVAL;
     LSSP_TRY(check_csr(n, n, Ap[n], Ap, Aj));
     if (Ap[n] < 1) return LSSP_AMD_EINVAL;
     if (level < 0) level = 1;  // pc.cxx: the reference's default iluk_level
+    if (level_out) *level_out = level;
     setup_mark(nullptr);
-    HostBCSR T;
     {
         HostCSR A;
         A.n = A.ncols = n;
@@ -1064,11 +1065,19 @@ int lssp_amd_bilu_create(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, c
         auto t0 = std::chrono::steady_clock::now();
         HostCSR L, U;
         std::vector<double> inv;
-        LSSP_TRY(bilu_factor(c, n, Ap, Aj, Ax, level, bs, L, U, inv));
+        HostBCSR T;
+        int lvl = level;
+        LSSP_TRY(bilu_factor(c, n, Ap, Aj, Ax, level, bs, L, U, inv, T, &lvl));
         lssp_amd_ilu *M = new lssp_amd_ilu();
         M->ctx = c;
         M->n = n;
         M->bs = bs;
+        M->c_level = lvl;
+        if (bs <= BILU_MAX_BS_DEV) {  // what lssp_amd_bilu_refactor needs of the pattern: 5 B per block, host
+            M->bBp = std::move(T.Bp);
+            M->bBj = std::move(T.Bj);
+            M->bIn = std::move(T.in_graph);
+        }
         M->Dinv = std::move(inv);
         M->Lp = std::move(L.Ap);
         M->Lj = std::move(L.Aj);
@@ -1080,6 +1089,37 @@ int lssp_amd_bilu_create(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, c
     } catch (const std::exception &) {
         return LSSP_AMD_ENOMEM;
     }
+}
+
+// New values on the same block pattern: scatter, graph compare, k_bilu0_level
+// over the kept level lists, U scaling, both record streams refilled
+// (bilu_factor.hip bilu_refactor_device); packet schedules, shadows and claim
+// counters stay as lssp_amd_bilu_create left them.
+int lssp_amd_bilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A)
+{
+    if (!c || !M || !A) return LSSP_AMD_EINVAL;
+    const bool eligible = M->bs >= 1 && M->bs <= BILU_MAX_BS_DEV && !M->bBp.empty() && M->line.ntiles == 0 &&
+                          M->lower.pk6_n > 0 && M->upper.pk6_n > 0 && M->d_Dinv;
+    if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
+    if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
+    try {
+        LSSP_HIP(hipSetDevice(c->device));
+        LSSP_TRY(bilu_refactor_device(c, M, A));
+        // the device factors are ahead of Lx / Ux / Dinv now, and of the sync-free
+        // arrays a single sweep built from those: the next reader refreshes the
+        // host copies, the next lssp_amd_ilu_trisolve rebuilds the arrays
+        std::lock_guard<std::mutex> lk(M->sync_free_mu);
+        M->host_stale = true;
+        for (TriSched *t : {&M->lower, &M->upper}) {
+            for (void *p : {(void *)t->perm, (void *)t->rp, (void *)t->cols, (void *)t->vals, (void *)t->diag})
+                if (p) (void)hipFree(p);
+            t->perm = t->rp = t->cols = nullptr;
+            t->vals = t->diag = nullptr;
+        }
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+    return LSSP_AMD_OK;
 }
 
 int lssp_amd_bilu_factor_host(int n, const int *Ap, const int *Aj, const double *Ax, int level, int bs, int *nnzL,
@@ -1115,7 +1155,8 @@ int lssp_amd_bilu_factor_host(int n, const int *Ap, const int *Aj, const double 
         if (!Lp || !Lx || !Dinv || !Up || !Uj || !Ux) return LSSP_AMD_EINVAL;
         HostCSR L, U;
         std::vector<double> inv;
-        LSSP_TRY(bilu_factor(nullptr, n, Ap, Aj, Ax, level, bs, L, U, inv));
+        HostBCSR T;
+        LSSP_TRY(bilu_factor(nullptr, n, Ap, Aj, Ax, level, bs, L, U, inv, T));
         *nnzL = L.Ap[n];
         *nnzU = U.Ap[n];
         memcpy(Lp, L.Ap.data(), sizeof(int) * (n + 1));
@@ -1177,6 +1218,8 @@ int lssp_amd_ilu_get_diag(const lssp_amd_ilu *M, int *bs, double *Dinv)
 {
     if (!M || !bs) return LSSP_AMD_EINVAL;
     *bs = M->bs;
+    // after lssp_amd_bilu_refactor the host copy is brought up to date here
+    if (M->bs > 0 && Dinv) LSSP_TRY(refactor_host_factors(const_cast<lssp_amd_ilu *>(M)));
     if (M->bs > 0 && Dinv) memcpy(Dinv, M->Dinv.data(), sizeof(double) * M->Dinv.size());
     return LSSP_AMD_OK;
 }
@@ -1189,6 +1232,7 @@ int lssp_amd_ilu_destroy(lssp_amd_ilu *M)
     free_trisched(M->upper);
     free_line_sweep(M->line);
     refactor_plan_free(M->rf);
+    bilu_plan_free(M->brf);
     if (M->d_cache) (void)hipFree(M->d_cache);
     for (double *p : M->d_sh)
         if (p) (void)hipFree(p);

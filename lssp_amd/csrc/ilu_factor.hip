@@ -375,6 +375,7 @@ int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx)
 // the host copies Lx / Ux from the device factors (ilu_factor's split)
 int refactor_host_factors(lssp_amd_ilu *M)
 {
+    if (M->brf) return bilu_refactor_host_factors(M);  // a BILUK handle (lssp_amd_bilu_refactor)
     if (!M->host_stale || !M->rf) return LSSP_AMD_OK;
     lssp_amd_ctx *c = M->ctx;
     const int n = M->n;

@@ -588,6 +588,7 @@ int bilu_pattern(const HostCSR &A, int level, int bs, HostBCSR &T)
     T.Bp = std::move(S.Ap);
     T.Bj = std::move(S.Aj);
     T.Bx.assign(T.Bj.size() * (size_t)bs2, 0.0);
+    T.in_graph.assign(T.Bj.size(), 0);
     std::vector<int> at(nb, -1);
     for (int i = 0; i < nb; i++) {
         for (int k = T.Bp[i]; k < T.Bp[i + 1]; k++) at[T.Bj[k]] = k;
@@ -595,6 +596,7 @@ int bilu_pattern(const HostCSR &A, int level, int bs, HostBCSR &T)
             for (int k = A.Ap[r]; k < A.Ap[r + 1]; k++) {
                 const int c = A.Aj[k];
                 T.Bx[(size_t)at[c / bs] * bs2 + (c % bs) * bs + r % bs] = A.Ax[k];
+                T.in_graph[at[c / bs]] = 1;
             }
     }
     return LSSP_AMD_OK;
@@ -637,7 +639,7 @@ int bilu0_factor_host(HostBCSR &T, std::vector<double> &inv)
 // lssp_pc_bilu_bcsr_to_lu (pc-biluk.cxx:104-196): L = the strict-lower blocks
 // and a unit diagonal LAST, U = a unit diagonal FIRST and inv_i * a_ij for
 // j > i; columns ascending, every entry of a block kept (zeros included).
-void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, HostCSR &U)
+void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, HostCSR &U, bool scaled)
 {
     const int nb = T.nb, bs = T.bs, bs2 = bs * bs, n = nb * bs;
     L = HostCSR();
@@ -682,7 +684,8 @@ void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, 
                         }
                     ol += bs;
                 } else if (j > i) {
-                    bilu_gemm(inv.data() + (size_t)i * bs2, a, 1., cache.data(), 0., bs);
+                    if (scaled) std::copy(a, a + bs2, cache.begin());
+                    else bilu_gemm(inv.data() + (size_t)i * bs2, a, 1., cache.data(), 0., bs);
                     for (int r = 0; r < bs; r++)
                         for (int c = 0; c < bs; c++) {
                             U.Aj[U.Ap[i * bs + r] + ou + c] = j * bs + c;

@@ -261,6 +261,29 @@ struct RefactorPlan {
     int *d_flag = nullptr;     // the pattern compare's answer
 };
 
+// lssp_amd_bilu_refactor's state (bilu_factor.hip), kept between refactors: the
+// block factor pattern (Bp, Bj: what bilu_pattern made, fill blocks included),
+// per block its block row and whether the creating matrix's block graph held
+// it, and the buffers the numeric block ILU(0) works in.  d_Bx / d_inv are
+// scratch: a refused call (pattern, singular block) dirties only them.  d_Fx is
+// the committed copy -- strict-lower blocks as factored, blocks right of the
+// diagonal already scaled by the row's inverse (bilu_expand's U values) -- which
+// the packet refill and the lazy host refresh read; it changes together with
+// the record streams and the handle's d_Dinv, after both flags are read.
+// Device bytes: 16 bs^2 + 10 per block, 8 bs^2 + 12 per block row.
+struct BiluPlan {
+    int nb = 0, bs = 0;
+    long nblk = 0;
+    int *d_Bp = nullptr, *d_Bj = nullptr, *d_Brow = nullptr;
+    unsigned char *d_in = nullptr;   // 1: a block of the creating matrix's graph (not fill)
+    unsigned char *d_hit = nullptr;  // the scatter's marks, compared with d_in
+    double *d_Bx = nullptr, *d_inv = nullptr, *d_Fx = nullptr;
+    int *d_first = nullptr;    // each block row's first non-lower block (Bp[i + 1] when none)
+    int *d_rows = nullptr;     // block rows ordered by level of the strict-lower block DAG
+    std::vector<int> lev_off;  // host: d_rows[lev_off[l] .. lev_off[l + 1]) is level l
+    int *d_flag = nullptr;     // [0] pattern rule broken, [1] singular diagonal block
+};
+
 }  // namespace lssp_amd
 
 struct lssp_amd_ilu {
@@ -288,7 +311,14 @@ struct lssp_amd_ilu {
     // c_kind 0 = caller-made factors (from_factors / from_ldu / BILUK)
     int c_kind = 0, c_level = 0, c_blk = 0;
     lssp_amd::RefactorPlan *rf = nullptr;  // built by the first lssp_amd_ilu_refactor
-    bool host_stale = false;  // Lx / Ux are older than the device factors (refreshed by get_factors)
+    bool host_stale = false;  // Lx / Ux (BILUK: and Dinv) are older than the device factors (refreshed by their readers)
+    // lssp_amd_bilu_create, bs <= 8 (lssp_amd_bilu_refactor's eligibility test and
+    // plan): the block factor pattern -- L / U cannot give it back, a block row
+    // without its diagonal block looks the same there -- and per block whether
+    // the creating matrix's block graph held it; the level is c_level
+    std::vector<int> bBp, bBj;
+    std::vector<unsigned char> bIn;
+    lssp_amd::BiluPlan *brf = nullptr;  // built by the first lssp_amd_bilu_refactor
     // made by lssp_amd_ilu_create_dev: the host copies Lp .. Ux do not exist until
     // something reads them (refactor_host_factors splits them from the device F);
     // until then the entry counts are these
@@ -426,6 +456,7 @@ struct HostBCSR {
     int nb = 0, bs = 1;
     std::vector<int> Bp, Bj;  // block rows; block columns ascending
     std::vector<double> Bx;   // bs x bs blocks, column-major
+    std::vector<unsigned char> in_graph;  // per block: A holds an entry of it (0: a fill block of level > 0)
 };
 // A (columns sorted) to BCSR on the level-k block pattern; EINVAL when n % bs != 0
 int bilu_pattern(const HostCSR &A, int level, int bs, HostBCSR &T);
@@ -433,7 +464,25 @@ int bilu_pattern(const HostCSR &A, int level, int bs, HostBCSR &T);
 // singular diagonal block.  The GPU one (bs <= 8) is bitwise the host one.
 int bilu0_factor_host(HostBCSR &T, std::vector<double> &inv);
 int bilu0_factor_gpu(lssp_amd_ctx *c, HostBCSR &T, std::vector<double> &inv);
-void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, HostCSR &U);
+// scaled: the blocks right of the diagonal already hold inv_i * a_ij (BiluPlan::d_Fx)
+void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, HostCSR &U, bool scaled = false);
+// block rows ordered by level of the strict-lower block DAG (k_bilu0_level's
+// launches): rows[off[l] .. off[l + 1]) is level l, ascending inside a level
+void bilu_levels(int nb, const std::vector<int> &Bp, const std::vector<int> &Bj, std::vector<int> &off,
+                 std::vector<int> &rows);
+// lssp_amd_bilu_refactor (capi.cpp).  bilu_factor.hip: the plan from the kept
+// block pattern; the device steps (scatter, graph compare, k_bilu0_level, U
+// scaling, packet refill, d_Dinv), EINVAL with the handle's live state untouched
+// when A breaks the pattern rule or a diagonal block is singular; Lx / Ux / Dinv
+// from the committed device values.
+int bilu_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M);
+void bilu_plan_free(BiluPlan *p);
+int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A);
+int bilu_refactor_host_factors(lssp_amd_ilu *M);
+// trisolve.hip: the V array of every packet record of t rewritten from the
+// committed block values Fx (k_pk6_refill); C, D, ROW and everything else stay
+int launch_pk6_refill(lssp_amd_ctx *c, const TriSched &t, bool upper, int bs, int nb, const int *Bp, const int *Bj,
+                      const int *first, const double *Fx);
 // z = D y of a BILUK apply.  pos != nullptr: y and z are indexed by schedule
 // position, row r at pos[r] (the packet sweeps' shadows); else natural order
 int launch_bdiag(lssp_amd_ctx *c, int n, int bs, const double *Dinv, const int *pos, const double *y, double *z);

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "bilu_refactor_dev.h"
 #include "internal.h"
 
 namespace lssp_amd {
@@ -654,6 +655,58 @@ static int launch_pk6(lssp_amd_ctx *c, const TriSched &t, const double *rhs, dou
         }
     }
     t.pk6_base += (unsigned long long)t.bp_nb + grid;
+    LSSP_HIP(hipGetLastError());
+    return LSSP_AMD_OK;
+}
+
+// New entry values into a sweep's packet records (lssp_amd_bilu_refactor): what
+// build_packets6 placed on the host, restated on the device.  A record names
+// each row's natural row (ROW) and fixes each entry's slot, so no host-made map
+// is needed.  One wave per packet (most packets of a general factor are far
+// below 256 rows), lane r takes rows r, r + 64, ..: for every entry pair the
+// lanes of a wave store consecutive 16-byte pairs.  C, D (1.0: unit diagonals),
+// ROW, the indices, descriptors, shadows and claim counters are pattern-only.
+template <int BS>
+__global__ __launch_bounds__(256) void k_pk6_refill(int npk, int EP, int upper, int nb, const int4 *__restrict__ desc,
+                                                    uint32_t *__restrict__ rec, const int *__restrict__ Bp,
+                                                    const int *__restrict__ Bj, const int *__restrict__ first,
+                                                    const double *__restrict__ Fx)
+{
+    const int lane = threadIdx.x & 63;
+    for (long p = blockIdx.x * 4L + (threadIdx.x >> 6); p < npk; p += (long)gridDim.x * 4) {
+        const int4 d = desc[p];
+        const int nr = d.z & 0x3ff;
+        uint32_t *w = rec + 4L * d.x;
+        const uint32_t *ROW = w + pk6_layout(EP, nr).row;
+        for (int r = lane; r < nr; r += 64)
+            pk6_refill_row(w, EP, nr, r, (int)ROW[r], upper != 0, BS, nb, Bp, Bj, first, Fx);
+    }
+}
+
+int launch_pk6_refill(lssp_amd_ctx *c, const TriSched &t, bool upper, int bs, int nb, const int *Bp, const int *Bj,
+                      const int *first, const double *Fx)
+{
+    if (t.pk6_n <= 0) return LSSP_AMD_EUNSUPPORTED;
+    const unsigned grid = (unsigned)std::min<long>(((long)t.pk6_n + 3) / 4, 16384);
+    const int4 *desc = reinterpret_cast<const int4 *>(t.pk6_desc);
+    switch (bs) {
+#define LSSP_PK6_REFILL(B)                                                                                         \
+    case B:                                                                                                        \
+        k_pk6_refill<B><<<grid, 256, 0, c->stream>>>(t.pk6_n, t.pk6_ep, upper ? 1 : 0, nb, desc, t.pk6_rec, Bp, Bj, \
+                                                     first, Fx);                                                   \
+        break;
+        LSSP_PK6_REFILL(1)
+        LSSP_PK6_REFILL(2)
+        LSSP_PK6_REFILL(3)
+        LSSP_PK6_REFILL(4)
+        LSSP_PK6_REFILL(5)
+        LSSP_PK6_REFILL(6)
+        LSSP_PK6_REFILL(7)
+        LSSP_PK6_REFILL(8)
+#undef LSSP_PK6_REFILL
+    default:
+        return LSSP_AMD_EUNSUPPORTED;
+    }
     LSSP_HIP(hipGetLastError());
     return LSSP_AMD_OK;
 }

@@ -384,6 +384,14 @@ class DILU:
         other handle raises LsspError with status 6 (unsupported) and stays as it was."""
         _ck(self.dev.L.lssp_amd_ilu_refactor(self.dev.h, self.h, A.h), "ilu_refactor")
 
+    def bilu_refactor(self, A: DMat):
+        """Factor a BILUK handle again from the values A holds now, on the block pattern it
+        was created with (lssp_amd_bilu_refactor): bs <= 8 handles on the packet sweeps; A
+        must have the creating matrix's block graph (status 1 otherwise, or for a singular
+        diagonal block); any other handle raises LsspError with status 6 (unsupported).  The
+        handle stays as it was in every such case."""
+        _ck(self.dev.L.lssp_amd_bilu_refactor(self.dev.h, self.h, A.h), "bilu_refactor")
+
     def apply(self, x: DVec, rhs: DVec):
         """x = U^-1 L^-1 rhs (lssp_pc_ilu_solve, solver-tri.cxx:57-60)"""
         _ck(self.dev.L.lssp_amd_ilu_apply(self.dev.h, self.h, x.ptr, rhs.ptr), "ilu_apply")
