@@ -94,10 +94,17 @@ int lssp_amd_mat_info(const lssp_amd_mat *A, int *nrows, int *ncols, int *nnz);
  * at most 16384 entries and the product stages that span of x in LDS instead
  * of gathering it from memory (locally numbered meshes); 0 otherwise. */
 int lssp_amd_mat_layout(const lssp_amd_mat *A, int *ndiag, int *windowed);
+/* Row coding of an offset-coded matrix: *npatterns > 0 when every row has at
+ * most 8 entries and the rows' offset-id sequences take at most 256 distinct
+ * values (a 7-pt grid has 27); the SpMV then reads one byte per row -- the
+ * index of the row's pattern -- instead of the row pointer and the ids (same
+ * entries, same summation order).  0: not row-coded. */
+int lssp_amd_mat_rowcodes(const lssp_amd_mat *A, int *npatterns);
 /* Device memory of a matrix: *csr_bytes = the resident CSR (Ap, Aj, Ax: every
  * operation but the two SpMV layouts above reads it), *aux_bytes = what the
- * SpMV layouts add beside it (offset ids + table; window spans and the sliced
- * copy, about as large as Aj + Ax again).  A windowed matrix whose padded
+ * SpMV layouts add beside it (offset ids + table; row codes + pattern table;
+ * window spans and the sliced copy, about as large as Aj + Ax again).  A
+ * windowed matrix whose padded
  * sliced copy would exceed 2^30 entries is not windowed (32-bit slice
  * offsets) and runs on the CSR product.  Either pointer may be NULL. */
 int lssp_amd_mat_bytes(const lssp_amd_mat *A, long long *csr_bytes, long long *aux_bytes);

@@ -480,6 +480,7 @@ static int upload_csr(lssp_amd_mat *M, const int *Ap, const int *Aj, const doubl
         LSSP_HIP(hipMemcpy(M->Ax, Ax, sizeof(double) * M->nnz, hipMemcpyHostToDevice));
     }
     LSSP_TRY(build_diag_ids(M, Ap, Aj));
+    LSSP_TRY(build_row_codes(M->ctx, M));
     return build_windows(M, Ap, Aj, Ax);
 }
 
@@ -516,6 +517,8 @@ int lssp_amd_mat_destroy(lssp_amd_mat *M)
     if (M->Ax) (void)hipFree(M->Ax);
     if (M->Ad) (void)hipFree(M->Ad);
     if (M->d_off) (void)hipFree(M->d_off);
+    if (M->Ac) (void)hipFree(M->Ac);
+    if (M->d_pat) (void)hipFree(M->d_pat);
     if (M->d_win) (void)hipFree(M->d_win);
     for (void *p : {(void *)M->s_ax, (void *)M->s_col, (void *)M->s_row, (void *)M->s_meta})
         if (p) (void)hipFree(p);
@@ -547,6 +550,13 @@ int lssp_amd_mat_layout(const lssp_amd_mat *A, int *ndiag, int *windowed)
     if (!A || !ndiag) return LSSP_AMD_EINVAL;
     *ndiag = A->ndiag;
     if (windowed) *windowed = A->d_win != nullptr;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_mat_rowcodes(const lssp_amd_mat *A, int *npatterns)
+{
+    if (!A || !npatterns) return LSSP_AMD_EINVAL;
+    *npatterns = A->npat;
     return LSSP_AMD_OK;
 }
 

@@ -555,6 +555,7 @@ int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal
     if (!ok) (void)hipGetLastError();  // clear the sticky error of a failed allocation
     LSSP_TRY(agree_status(c, ok ? LSSP_AMD_OK : LSSP_AMD_ENOMEM));
     LSSP_TRY(agree_status(c, build_diag_ids(M, Ap, lj.data())));  // the SpMV's column coding (capi.cpp)
+    LSSP_TRY(agree_status(c, build_row_codes(c, M)));              // and its row coding (convert.hip)
     guard.m = nullptr;
     *out = M;
     return LSSP_AMD_OK;

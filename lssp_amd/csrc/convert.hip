@@ -572,6 +572,110 @@ __global__ __launch_bounds__(CT) void k_off_ids(long nrows, const int *__restric
     }
 }
 
+// ---- the SpMV's row coding (lssp_amd_mat::Ac), from the resident Ap and Ad ----
+using lssp_amd::ROWPAT_LEN;
+using lssp_amd::ROWPAT_MAX;
+typedef unsigned long long pat_t;
+constexpr pat_t PAT_EMPTY = ~0ull;  // eight entries of id 254: such a row leaves the matrix uncoded
+constexpr int PAT_HS = 1024;        // hash slots of the pattern sets
+// the device-wide set's counters: distinct patterns seen, the flag of a matrix
+// that cannot be coded; its keys: PAT_HS hash slots, then the patterns in arrival order
+constexpr int P_COUNT = 0, P_OVER = 1;
+
+__device__ __forceinline__ unsigned pat_slot(pat_t k) { return (unsigned)((k * 0x9E3779B97F4A7C15ull) >> 54); }  // 10 bits
+
+__global__ __launch_bounds__(CT) void k_pat_init(pat_t *__restrict__ gk, int *__restrict__ gi)
+{
+    for (int t = threadIdx.x; t < PAT_HS + ROWPAT_MAX; t += CT) gk[t] = t < PAT_HS ? PAT_EMPTY : 0;
+    if (threadIdx.x < 2) gi[threadIdx.x] = 0;
+}
+
+// off_insert for 64-bit pattern keys; *full counts the claims, more than
+// ROWPAT_MAX of them stop further claims
+__device__ __forceinline__ bool pat_insert(pat_t *tab, const int *full, pat_t k)
+{
+    unsigned h = pat_slot(k);
+    for (int p = 0; p < PAT_HS; p++, h = (h + 1) & (PAT_HS - 1)) {
+        pat_t cur = *(volatile pat_t *)(tab + h);
+        if (cur == k) return false;
+        if (cur != PAT_EMPTY) continue;
+        if (*(volatile const int *)full > ROWPAT_MAX) return false;
+        pat_t old = atomicCAS(tab + h, PAT_EMPTY, k);
+        if (old == PAT_EMPTY) return true;
+        if (old == k) return false;
+    }
+    return false;
+}
+
+// a row's pattern key: byte k = Ad of its entry k, plus 1
+__device__ __forceinline__ pat_t pat_key(const uint8_t *__restrict__ Ad, int b, int e)
+{
+    pat_t key = 0;
+    for (int k = b; k < e; k++) key |= (pat_t)(Ad[k] + 1u) << (8 * (k - b));
+    return key;
+}
+
+// distinct row patterns, collected as k_off_collect collects offsets (10 M
+// rows hit 27 keys); a row of more than ROWPAT_LEN entries raises P_OVER
+__global__ __launch_bounds__(CT) void k_pat_collect(long nrows, const int *__restrict__ Ap,
+                                                    const uint8_t *__restrict__ Ad, pat_t *__restrict__ gk,
+                                                    int *__restrict__ gi)
+{
+    __shared__ pat_t tab[PAT_HS];
+    __shared__ int cnt;
+    for (int t = threadIdx.x; t < PAT_HS; t += CT) tab[t] = PAT_EMPTY;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        if (*(volatile int *)&cnt > ROWPAT_MAX || *(volatile int *)(gi + P_OVER)) break;
+        const int b = Ap[i], e = Ap[i + 1];
+        const pat_t key = e - b <= ROWPAT_LEN ? pat_key(Ad, b, e) : PAT_EMPTY;
+        if (key == PAT_EMPTY) {
+            atomicOr(gi + P_OVER, 1);
+            break;
+        }
+        if (pat_insert(tab, &cnt, key)) atomicAdd(&cnt, 1);
+    }
+    __syncthreads();
+    if (cnt > ROWPAT_MAX) {
+        if (threadIdx.x == 0) atomicOr(gi + P_OVER, 1);
+        return;
+    }
+    for (int t = threadIdx.x; t < PAT_HS; t += CT) {
+        pat_t k = tab[t];
+        if (k == PAT_EMPTY || !pat_insert(gk, gi + P_COUNT, k)) continue;
+        int at = atomicAdd(gi + P_COUNT, 1);
+        if (at < ROWPAT_MAX)
+            gk[PAT_HS + at] = k;
+        else
+            atomicOr(gi + P_OVER, 1);
+    }
+}
+
+// Ac[i] = index of row i's key in the ascending table pat[0, np)
+__global__ __launch_bounds__(CT) void k_pat_codes(long nrows, const int *__restrict__ Ap,
+                                                  const uint8_t *__restrict__ Ad, const pat_t *__restrict__ pat,
+                                                  int np, uint8_t *__restrict__ Ac)
+{
+    __shared__ pat_t tab[ROWPAT_MAX];
+    for (int t = threadIdx.x; t < np; t += CT) tab[t] = pat[t];
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        const pat_t key = pat_key(Ad, Ap[i], Ap[i + 1]);  // in the table by construction
+        int lo = 0, hi = np - 1;
+        while (lo < hi) {
+            int mid = (lo + hi) >> 1;
+            if (tab[mid] < key)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        Ac[i] = (uint8_t)lo;
+    }
+}
+
 // build_windows' first test (capi.cpp): does some WIN_ROWS-row block's column
 // span exceed WIN_CAP?  One workgroup per block
 __global__ __launch_bounds__(CT) void k_win_wide(long nb, int nrows, const int *__restrict__ Ap,
@@ -719,6 +823,49 @@ int bucket(Scratch &S, long nnz, const int *key, int nr, const int *sj, const do
 }
 
 }  // namespace
+
+// The row codes of an offset-coded matrix, from its resident Ap and Ad: one
+// routine for every construction path (upload, distributed upload, device
+// arrays), so the codes, the table and aux_bytes are the same on each.  The
+// patterns are numbered by ascending key, whatever order the rows arrived in.
+int lssp_amd::build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
+{
+    M->npat = 0;
+    if (M->ndiag == 0 || !M->Ad || M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(gk, pat_t, PAT_HS + ROWPAT_MAX);
+    SCRATCH(gi, int, 2);
+    k_pat_init<<<1, CT, 0, s>>>(gk, gi);
+    k_pat_collect<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ad, gk, gi);
+    LSSP_HIP(hipGetLastError());
+    int head[2];  // count, flag
+    std::vector<pat_t> pat(ROWPAT_MAX);
+    LSSP_HIP(hipMemcpyAsync(head, gi, sizeof(head), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipMemcpyAsync(pat.data(), gk + PAT_HS, sizeof(pat_t) * ROWPAT_MAX, hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipStreamSynchronize(s));
+    if (head[P_OVER] || head[P_COUNT] > ROWPAT_MAX || head[P_COUNT] <= 0) return LSSP_AMD_OK;  // not row-coded
+    pat.resize(head[P_COUNT]);
+    std::sort(pat.begin(), pat.end());
+    // +32: padded as Ad is
+    const size_t ac_bytes = (size_t)M->nrows + 32;
+    LSSP_HIP(hipMalloc(&M->Ac, ac_bytes));
+    LSSP_HIP(hipMalloc(&M->d_pat, sizeof(pat_t) * pat.size()));
+    LSSP_HIP(hipMemsetAsync(M->Ac + M->nrows, 0, 32, s));
+    LSSP_HIP(hipMemcpyAsync(M->d_pat, pat.data(), sizeof(pat_t) * pat.size(), hipMemcpyHostToDevice, s));
+    k_pat_codes<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ad, M->d_pat, (int)pat.size(), M->Ac);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(s));
+    // a key's length is the place of its highest non-zero byte, so the sorted keys' lengths ascend
+    for (int l = 0; l < ROWPAT_LEN; l++) {
+        int shorter = 0;
+        for (pat_t k : pat) shorter += (k >> (8 * l)) == 0;  // at most l entries
+        M->pat_thr[l] = (unsigned short)shorter;
+    }
+    M->aux_bytes += (long long)ac_bytes + (long long)sizeof(pat_t) * (long long)pat.size();
+    M->npat = (int)pat.size();
+    return LSSP_AMD_OK;
+}
 
 extern "C" {
 
@@ -1082,7 +1229,7 @@ static int diag_ids_dev(lssp_amd_ctx *c, lssp_amd_mat *M)
     M->max_off = 0;
     for (int o : off) M->max_off = std::max(M->max_off, std::abs(o));
     M->max_off_int = M->max_off;
-    return LSSP_AMD_OK;
+    return lssp_amd::build_row_codes(c, M);
 }
 
 // build_windows (capi.cpp) for a CSR in HBM: the span test runs on the device;

@@ -120,6 +120,18 @@ struct lssp_amd_mat {
     int *d_off = nullptr;
     int ndiag = 0;
     int max_off = 0;  // max |col - row| of the coded offsets
+    // row coding (SpMV): when an offset-coded matrix has rows of at most 8
+    // entries in at most ROWPAT_MAX distinct patterns (a row's ids in CSR
+    // order; a 7-pt grid has 27), Ac[i] indexes d_pat and the SpMV reads one
+    // byte per row instead of Ap's four and Ad's byte per entry.  Pattern key:
+    // byte k = id of entry k, plus 1 (0: no entry k); d_pat is ascending, so
+    // the patterns' lengths ascend with the code and pat_thr[l] = number of
+    // patterns shorter than l + 1 entries gives a code's length without the
+    // table (build_row_codes, convert.hip); npat == 0: not row-coded
+    uint8_t *Ac = nullptr;
+    unsigned long long *d_pat = nullptr;
+    int npat = 0;
+    unsigned short pat_thr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // max |col - row| over the rows of the halo-free chunks [ich0, ich1) of a
     // distributed matrix (its whole row range on one rank: max_off)
     int max_off_int = 0;
@@ -138,7 +150,7 @@ struct lssp_amd_mat {
     double *s_ax = nullptr;
     uint32_t *s_col = nullptr, *s_row = nullptr;
     int *s_meta = nullptr;
-    // device bytes held beside the CSR arrays (offset ids + table, window spans,
+    // device bytes held beside the CSR arrays (offset ids + table, row codes + table, window spans,
     // the sliced copy): lssp_amd_mat_bytes
     long long aux_bytes = 0;
     // k_spmv3's block streams, timed at upload (tune_spmv_streams); 0: the default 8
@@ -355,6 +367,10 @@ constexpr int WIN_ROWS = 1024, WIN_CAP = 16384;
 // open-addressing sets of DIAG_HS slots (host: build_diag_ids, capi.cpp;
 // device: lssp_amd_mat_from_device, convert.hip)
 constexpr int DIAG_MAX = 255, DIAG_HS = 1024;
+// row coding of an offset-coded matrix from its resident Ap / Ad (convert.hip):
+// at most ROWPAT_MAX patterns of at most ROWPAT_LEN entries, else npat stays 0
+constexpr int ROWPAT_MAX = 256, ROWPAT_LEN = 8;
+int build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M);
 int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, const double *x,
                 double beta, const double *y, double *z, int nred, const double *w0,
                 const double *w1, long cb = 0, long ce = -1);  // chunks [cb, ce); ce < 0: all

@@ -356,7 +356,7 @@ struct SpmvArgs {
     const double *w0, *w1;  // fused dot operands: red0 = z*w0, red1 = z*(w1 ? w1 : z), red2 = w0*w0
     double *part;
     long pcap;
-    const uint8_t *Ad;  // diagonal-id column coding (lssp_amd_mat::Ad), CMP kernels
+    const uint8_t *Ad;  // diagonal-id column coding (lssp_amd_mat::Ad), COL_ID kernels
     const int *off;
     int ndiag;
     const double *guard;  // lssp_amd_ctx::guard
@@ -364,6 +364,11 @@ struct SpmvArgs {
     int streams;          // concurrent block streams (a multiple of 8, spmv_streams)
     int pbpp, pz, pw;     // column-group block order (spmv_group_env): blocks per plane, planes, group width; 0: natural
     int ntv;              // w0 / w1 / z as non-temporal accesses
+    // row coding (lssp_amd_mat::Ac, d_pat, npat, pat_thr), COL_ROW kernels; npat == 0: not used
+    const uint8_t *Ac;
+    const unsigned long long *pat;
+    int npat;
+    unsigned short thr[8];
 };
 
 // The 256-row blocks are dealt so that each of the 8 XCDs owns one contiguous
@@ -375,16 +380,29 @@ struct SpmvArgs {
 // boundaries, clamped to the padded arrays; entries outside the block are
 // dropped when landing in LDS) and the lane's own Ap[r], Ap[r+1] -- so one
 // memory round trip covers the staging and the row bounds.
-// CMP: the columns come from the diagonal-id bytes (col = row + off[Ad[k]]),
-// 1 byte per entry instead of 4 (7-pt: 0.83 of the CSR bytes per product).
-template <int EPI, int NRED, bool CMP>
+// CM, the column mode: COL_J reads Aj; COL_ID takes the columns from the
+// diagonal-id bytes (col = row + off[Ad[k]]), 1 byte per entry instead of 4
+// (7-pt: 0.83 of the CSR bytes per product); COL_ROW takes them from the row's
+// pattern (lssp_amd_mat::Ac: col = row + off[id k of pat[Ac[row]]]), 1 byte
+// per row instead of Ap's 4 and a byte per entry (7-pt: 0.88 of COL_ID's
+// bytes).  A COL_ROW lane takes its row's length from the code alone (the
+// patterns' lengths ascend with the code: SpmvArgs::thr) and its row's start
+// from a scan of the block's lengths -- a wave scan, the wave totals handed
+// through LDS across the staging barrier -- onto Ap[r0]; only Ax is staged,
+// and every row has at most 8 entries, so a block always fits SPMV_CAP.
+enum { COL_J = 0, COL_ID = 1, COL_ROW = 2 };
+template <int EPI, int NRED, int CM>
 __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
 {
+    constexpr bool CMP = CM == COL_ID, ROW = CM == COL_ROW;
+    static_assert(256 * 8 <= SPMV_CAP, "a row-coded block fits the staging buffer");
     constexpr int NX2 = (SPMV_CAP / 2 + 1 + 255) / 256;  // double2 loads per lane
     constexpr int NJ4 = CMP ? 1 : (SPMV_CAP / 4 + 1 + 255) / 256;  // int4 loads per lane (16 ids when CMP)
     __shared__ __attribute__((aligned(16))) double sx[SPMV_CAP + 2];
-    __shared__ __attribute__((aligned(16))) int sj[CMP ? SPMV_CAP / 4 + 8 : SPMV_CAP + 4];
-    __shared__ int soff[CMP ? 256 : 1];
+    __shared__ __attribute__((aligned(16))) int sj[ROW ? 1 : CMP ? SPMV_CAP / 4 + 8 : SPMV_CAP + 4];
+    __shared__ int soff[CM != COL_J ? 256 : 1];
+    __shared__ unsigned long long spat[ROW ? 256 : 1];
+    __shared__ int swt[ROW ? 4 : 1];  // the waves' entry counts
     __shared__ double lds[MAX_SLOTS][4];
     // the guard is read with the row bounds and tested before the entries are
     // loaded: its round trip overlaps theirs instead of preceding it
@@ -404,7 +422,10 @@ __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_p
     const int base = a.Ap[r0];
     const int cnt = a.Ap[rend] - base;
     const int rr = min(r, a.nrows - 1);
-    const int rb = a.Ap[rr], re = a.Ap[rr + 1];
+    int rb = 0, re = 0;
+    unsigned code = 0;
+    if (ROW) code = a.Ac[rr];
+    else rb = a.Ap[rr], re = a.Ap[rr + 1];
     // the fused dots' second operands, loaded up front with the row bounds (the
     // compiler may not move them above the z store: w0 / w1 may alias z, and
     // then they are read as the value just stored, zv, below)
@@ -420,7 +441,7 @@ __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_p
     }
     if (gv != 0.0) return;  // a batched iteration past the stop (lssp_amd_ctx::guard)
     double sum = 0;
-    if (cnt <= SPMV_CAP) {
+    if (ROW || cnt <= SPMV_CAP) {
         typedef double dbl2_t __attribute__((ext_vector_type(2)));
         typedef int int4_t __attribute__((ext_vector_type(4)));
         // CMP: jb / jmax / jn count 16-byte vectors of ids (16 entries each)
@@ -431,24 +452,65 @@ __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_p
         const long last = cnt > 0 ? (long)base + cnt - 1 : (long)base;
         const long xmax = min(last >> 1, (nnz_pad >> 1) - 1);
         const long jmax = min(last >> JS, (CMP ? (nnz_pad - 4 + 32) >> 4 : nnz_pad >> 2) - 1);
-        if (CMP && tid < a.ndiag) soff[tid] = a.off[tid];
+        if (CM != COL_J && tid < a.ndiag) soff[tid] = a.off[tid];
+        if (ROW && tid < a.npat) spat[tid] = a.pat[tid];
         const dbl2_t *X2 = reinterpret_cast<const dbl2_t *>(a.Ax);
         const int4_t *J4 = CMP ? reinterpret_cast<const int4_t *>(a.Ad) : reinterpret_cast<const int4_t *>(a.Aj);
         dbl2_t vx[NX2];
-        int4_t vj[NJ4];
+        int4_t vj[ROW ? 1 : NJ4];
 #pragma unroll
         for (int u = 0; u < NX2; u++) vx[u] = __builtin_nontemporal_load(X2 + min((xb >> 1) + tid + 256 * u, xmax));
+        if (!ROW) {
 #pragma unroll
-        for (int u = 0; u < NJ4; u++) vj[u] = __builtin_nontemporal_load(J4 + min((jb >> JS) + tid + 256 * u, jmax));
+            for (int u = 0; u < NJ4; u++) vj[u] = __builtin_nontemporal_load(J4 + min((jb >> JS) + tid + 256 * u, jmax));
+        }
         const int xn = (int)(xmax - (xb >> 1)) + 1, jn = (int)(jmax - (jb >> JS)) + 1;  // vectors in range
+        // ROW: the row's length from its code, then its start inside the block:
+        // an inclusive scan of the wave's lengths, the wave's total to LDS
+        int len = 0, inc = 0;
+        if (ROW) {
+#pragma unroll
+            for (int l = 0; l < 8; l++) len += code >= (unsigned)a.thr[l];
+            if (r >= a.nrows) len = 0;
+            const int lane = tid & 63;
+            inc = len;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = __shfl_up(inc, d, 64);
+                if (lane >= d) inc += t;
+            }
+            if (lane == 63) swt[tid >> 6] = inc;
+        }
 #pragma unroll
         for (int u = 0; u < NX2; u++)
             if (tid + 256 * u < xn) reinterpret_cast<dbl2_t *>(sx)[tid + 256 * u] = vx[u];
+        if (!ROW) {
 #pragma unroll
-        for (int u = 0; u < NJ4; u++)
-            if (tid + 256 * u < jn) reinterpret_cast<int4_t *>(sj)[tid + 256 * u] = vj[u];
+            for (int u = 0; u < NJ4; u++)
+                if (tid + 256 * u < jn) reinterpret_cast<int4_t *>(sj)[tid + 256 * u] = vj[u];
+        }
         __syncthreads();
-        if (r < a.nrows) {
+        if (ROW) {
+            if (len > 0) {
+                const int wave = tid >> 6;
+                int lo = inc - len;  // the row's first entry, counted from the block's
+                if (wave > 0) lo += swt[0];
+                if (wave > 1) lo += swt[1];
+                if (wave > 2) lo += swt[2];
+                const double *sr = sx + ((int)(base - xb) + lo);
+                const unsigned long long pt = spat[code];
+                // as below: all x gathers in flight, the products added in CSR order
+                double pr[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int k = min(u, len - 1);
+                    pr[u] = a.x[r + soff[(int)((pt >> (8 * k)) & 255u) - 1]] * sr[k];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++)
+                    if (u < len) sum += pr[u];
+            }
+        } else if (r < a.nrows) {
             const int ox = (int)(base - xb) - base, oj = (int)(base - jb) - base;
             const int len = re - rb;
             const unsigned char *sd = reinterpret_cast<const unsigned char *>(sj);
@@ -740,27 +802,38 @@ static int spmv_streams_env()
     }();
     return k;
 }
+// LSSP_AMD_SPMV_ROWCODE=0: a row-coded matrix's product reads the ids
+// (COL_ID) all the same (tests, A/B runs)
+static int spmv_rowcode()
+{
+    static const int k = [] {
+        const char *e = getenv("LSSP_AMD_SPMV_ROWCODE");
+        return e ? atoi(e) : 1;
+    }();
+    return k;
+}
 static int spmv_streams(const lssp_amd_mat *A)
 {
     const int e = spmv_streams_env();
     return e ? e : A->streams > 0 ? A->streams : 8;
 }
 
-template <int EPI, bool CMP>
+template <int EPI, int CM>
 static void spmv_dispatch(const SpmvArgs &a, int nred, long nblocks, hipStream_t s, long nnz_pad)
 {
     const long g = (nblocks + a.streams - 1) / a.streams * a.streams;  // a multiple of K: whole stream shares
-    if (nred == 0) k_spmv3<EPI, 0, CMP><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
-    else if (nred == 1) k_spmv3<EPI, 1, CMP><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
-    else if (nred == 2 || EPI != EPI_AMX) k_spmv3<EPI, 2, CMP><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
-    else k_spmv3<EPI_AMX, 3, CMP><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+    if (nred == 0) k_spmv3<EPI, 0, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+    else if (nred == 1) k_spmv3<EPI, 1, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+    else if (nred == 2 || EPI != EPI_AMX) k_spmv3<EPI, 2, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+    else k_spmv3<EPI_AMX, 3, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
 }
 
 template <int EPI>
 static void spmv_dispatch(const SpmvArgs &a, int nred, long nblocks, hipStream_t s, long nnz_pad)
 {
-    if (a.ndiag > 0) spmv_dispatch<EPI, true>(a, nred, nblocks, s, nnz_pad);
-    else spmv_dispatch<EPI, false>(a, nred, nblocks, s, nnz_pad);
+    if (a.npat > 0) spmv_dispatch<EPI, COL_ROW>(a, nred, nblocks, s, nnz_pad);
+    else if (a.ndiag > 0) spmv_dispatch<EPI, COL_ID>(a, nred, nblocks, s, nnz_pad);
+    else spmv_dispatch<EPI, COL_J>(a, nred, nblocks, s, nnz_pad);
 }
 
 int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, const double *x,
@@ -778,7 +851,14 @@ int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, c
     const long nb = ce - cb;
     if (nb == 0) return LSSP_AMD_OK;
     SpmvArgs a{A->nrows, A->Ap, A->Aj, A->Ax, x, y, z, alpha, beta, w0, w1, c->d_part, c->part_cap,
-               A->Ad, A->d_off, A->ndiag, c->guard, cb, spmv_streams(A), 0, 0, 0, spmv_ntv()};
+               A->Ad, A->d_off, A->ndiag, c->guard, cb, spmv_streams(A), 0, 0, 0, spmv_ntv(),
+               nullptr, nullptr, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
+    if (A->npat > 0 && spmv_rowcode()) {
+        a.Ac = A->Ac;
+        a.pat = A->d_pat;
+        a.npat = A->npat;
+        memcpy(a.thr, A->pat_thr, sizeof(a.thr));
+    }
     const long plane = A->max_off_int;
     if (A->ndiag > 0 && plane >= 256 * 8 && plane % 256 == 0) {
         const long bpp = plane / 256;

@@ -246,6 +246,14 @@ class DMat:
         return v.value
 
     @property
+    def rowcodes(self) -> int:
+        """> 0: the SpMV reads one pattern byte per row (that many patterns) instead of the
+        row pointers and the ids"""
+        v = ctypes.c_int()
+        _ck(self.dev.L.lssp_amd_mat_rowcodes(self.h, ctypes.byref(v)), "mat_rowcodes")
+        return v.value
+
+    @property
     def windowed(self) -> bool:
         """the SpMV stages each 1024-row block's x span in LDS (k_spmv_win)"""
         v, w = ctypes.c_int(), ctypes.c_int()
