@@ -100,10 +100,18 @@ int lssp_amd_mat_layout(const lssp_amd_mat *A, int *ndiag, int *windowed);
  * index of the row's pattern -- instead of the row pointer and the ids (same
  * entries, same summation order).  0: not row-coded. */
 int lssp_amd_mat_rowcodes(const lssp_amd_mat *A, int *npatterns);
+/* Value coding of a row-coded matrix: *nvalues > 0 when its rows -- pattern
+ * and values, compared bit for bit -- take at most 256 distinct values (a
+ * constant-coefficient 7-pt grid has 27); the SpMV then reads one byte per
+ * row -- the index of the row in a table of those rows -- and none of the
+ * matrix values (same entries, same summation order).  The codes follow the
+ * values: lssp_amd_mat_update_values rebuilds or drops them.  0: not
+ * value-coded (always for a distributed matrix). */
+int lssp_amd_mat_valcodes(const lssp_amd_mat *A, int *nvalues);
 /* Device memory of a matrix: *csr_bytes = the resident CSR (Ap, Aj, Ax: every
  * operation but the two SpMV layouts above reads it), *aux_bytes = what the
  * SpMV layouts add beside it (offset ids + table; row codes + pattern table;
- * window spans and the sliced copy, about as large as Aj + Ax again).  A
+ * value codes + value table; window spans and the sliced copy, about as large as Aj + Ax again).  A
  * windowed matrix whose padded
  * sliced copy would exceed 2^30 entries is not windowed (32-bit slice
  * offsets) and runs on the CSR product.  Either pointer may be NULL. */

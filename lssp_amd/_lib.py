@@ -53,6 +53,7 @@ SIGNATURES = {
     "lssp_amd_mat_info": (_ci, [_vp, _vp, _vp, _vp]),
     "lssp_amd_mat_layout": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_mat_rowcodes": (_ci, [_vp, _vp]),
+    "lssp_amd_mat_valcodes": (_ci, [_vp, _vp]),
     "lssp_amd_mat_bytes": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_ilu_sweep_layout": (_ci, [_vp, _vp, _vp, _vp]),
     "lssp_amd_mv_amxpby": (_ci, [_vp, _cd, _vp, _vp, _cd, _vp]),

@@ -481,6 +481,7 @@ static int upload_csr(lssp_amd_mat *M, const int *Ap, const int *Aj, const doubl
     }
     LSSP_TRY(build_diag_ids(M, Ap, Aj));
     LSSP_TRY(build_row_codes(M->ctx, M));
+    LSSP_TRY(build_val_codes(M->ctx, M));
     return build_windows(M, Ap, Aj, Ax);
 }
 
@@ -519,6 +520,9 @@ int lssp_amd_mat_destroy(lssp_amd_mat *M)
     if (M->d_off) (void)hipFree(M->d_off);
     if (M->Ac) (void)hipFree(M->Ac);
     if (M->d_pat) (void)hipFree(M->d_pat);
+    if (M->Av) (void)hipFree(M->Av);
+    if (M->d_val) (void)hipFree(M->d_val);
+    if (M->d_voff) (void)hipFree(M->d_voff);
     if (M->d_win) (void)hipFree(M->d_win);
     for (void *p : {(void *)M->s_ax, (void *)M->s_col, (void *)M->s_row, (void *)M->s_meta})
         if (p) (void)hipFree(p);
@@ -557,6 +561,13 @@ int lssp_amd_mat_rowcodes(const lssp_amd_mat *A, int *npatterns)
 {
     if (!A || !npatterns) return LSSP_AMD_EINVAL;
     *npatterns = A->npat;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_mat_valcodes(const lssp_amd_mat *A, int *nvalues)
+{
+    if (!A || !nvalues) return LSSP_AMD_EINVAL;
+    *nvalues = A->nval;
     return LSSP_AMD_OK;
 }
 

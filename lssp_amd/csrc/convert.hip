@@ -29,6 +29,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdlib>
 #include <vector>
@@ -676,6 +677,148 @@ __global__ __launch_bounds__(CT) void k_pat_codes(long nrows, const int *__restr
     }
 }
 
+// ---- the SpMV's value coding (lssp_amd_mat::Av), from the resident Ap, Ac and Ax ----
+// A row's key is its pattern and the bit patterns of its values in CSR order:
+// nine 64-bit words, the pattern key (d_pat[Ac[i]]: ascending with the code)
+// and eight values (+0.0 past the row's length, which the pattern fixes).  The
+// rows are collected by a 64-bit mix of the key in the pattern sets above, each
+// distinct mix with one row that produced it; the table is then those rows'
+// keys, and k_val_codes compares every row with the table in full, so two keys
+// that share a mix leave the matrix uncoded instead of miscoded.
+using lssp_amd::ROWVAL_MAX;
+static_assert(ROWVAL_MAX == ROWPAT_MAX, "the value sets are the pattern sets (pat_insert's bound)");
+constexpr int VAL_WORDS = 1 + ROWPAT_LEN;
+
+__device__ __forceinline__ pat_t val_mix(pat_t h, pat_t v)
+{
+    h = (h ^ v) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 32);
+}
+
+__device__ __forceinline__ pat_t val_hash(unsigned code, const double *__restrict__ Ax, int b, int e)
+{
+    pat_t h = val_mix(0x243F6A8885A308D3ull, code);
+    for (int k = b; k < e; k++) h = val_mix(h, (pat_t)__double_as_longlong(Ax[k]));
+    return h == PAT_EMPTY ? h - 1 : h;
+}
+
+// pat_insert that reports the slot it claimed (-1: the key was there, or the set is full)
+__device__ __forceinline__ int pat_claim(pat_t *tab, const int *full, pat_t k)
+{
+    unsigned h = pat_slot(k);
+    for (int p = 0; p < PAT_HS; p++, h = (h + 1) & (PAT_HS - 1)) {
+        pat_t cur = *(volatile pat_t *)(tab + h);
+        if (cur == k) return -1;
+        if (cur != PAT_EMPTY) continue;
+        if (*(volatile const int *)full > ROWVAL_MAX) return -1;
+        pat_t old = atomicCAS(tab + h, PAT_EMPTY, k);
+        if (old == PAT_EMPTY) return (int)h;
+        if (old == k) return -1;
+    }
+    return -1;
+}
+
+// distinct value rows, as k_pat_collect collects patterns: rep[at] = one row of
+// the at-th distinct mix.  More than ROWVAL_MAX of them raise P_OVER, and every
+// workgroup stops at its next row (a matrix of varying coefficients pays a
+// fraction of one pass)
+__global__ __launch_bounds__(CT) void k_val_collect(long nrows, const int *__restrict__ Ap,
+                                                    const uint8_t *__restrict__ Ac, const double *__restrict__ Ax,
+                                                    pat_t *__restrict__ gk, int *__restrict__ gi,
+                                                    int *__restrict__ rep)
+{
+    __shared__ pat_t tab[PAT_HS];
+    __shared__ int trow[PAT_HS];
+    __shared__ int cnt;
+    for (int t = threadIdx.x; t < PAT_HS; t += CT) tab[t] = PAT_EMPTY;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        if (*(volatile int *)&cnt > ROWVAL_MAX || *(volatile int *)(gi + P_OVER)) break;
+        const int at = pat_claim(tab, &cnt, val_hash(Ac[i], Ax, Ap[i], Ap[i + 1]));
+        if (at >= 0) {
+            trow[at] = (int)i;
+            atomicAdd(&cnt, 1);
+        }
+    }
+    __syncthreads();
+    if (cnt > ROWVAL_MAX) {
+        if (threadIdx.x == 0) atomicOr(gi + P_OVER, 1);
+        return;
+    }
+    for (int t = threadIdx.x; t < PAT_HS; t += CT) {
+        pat_t k = tab[t];
+        if (k == PAT_EMPTY || !pat_insert(gk, gi + P_COUNT, k)) continue;
+        int at = atomicAdd(gi + P_COUNT, 1);
+        if (at < ROWVAL_MAX)
+            rep[at] = trow[t];
+        else
+            atomicOr(gi + P_OVER, 1);
+    }
+}
+
+// row i's key, word q
+__device__ __forceinline__ pat_t val_word(int q, pat_t pt, const double *__restrict__ Ax, int b, int len)
+{
+    if (q == 0) return pt;
+    return q - 1 < len ? (pat_t)__double_as_longlong(Ax[b + q - 1]) : 0;
+}
+
+// out[VAL_WORDS * t + q] = word q of row rep[t]'s key
+__global__ __launch_bounds__(CT) void k_val_gather(int nrep, const int *__restrict__ rep, const int *__restrict__ Ap,
+                                                   const uint8_t *__restrict__ Ac, const double *__restrict__ Ax,
+                                                   const pat_t *__restrict__ pat, pat_t *__restrict__ out)
+{
+    const int t = threadIdx.x;
+    if (t >= nrep) return;
+    const int i = rep[t], b = Ap[i], len = Ap[i + 1] - b;
+    for (int q = 0; q < VAL_WORDS; q++) out[VAL_WORDS * t + q] = val_word(q, pat[Ac[i]], Ax, b, len);
+}
+
+// Av[i] = index of row i's key in the ascending table val (word q of entry c
+// at val[q * nv + c]), found by bisection and then compared word for word: a
+// row that is not in the table raises *bad
+__global__ __launch_bounds__(CT) void k_val_codes(long nrows, const int *__restrict__ Ap,
+                                                  const uint8_t *__restrict__ Ac, const double *__restrict__ Ax,
+                                                  const pat_t *__restrict__ pat, int np,
+                                                  const pat_t *__restrict__ val, int nv, uint8_t *__restrict__ Av,
+                                                  int *__restrict__ bad)
+{
+    __shared__ pat_t spat[ROWPAT_MAX];
+    __shared__ pat_t sv[VAL_WORDS][ROWVAL_MAX];
+    for (int t = threadIdx.x; t < np; t += CT) spat[t] = pat[t];
+    for (int t = threadIdx.x; t < VAL_WORDS * nv; t += CT) sv[t / nv][t % nv] = val[t];
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        const int b = Ap[i], len = Ap[i + 1] - b;
+        pat_t key[VAL_WORDS];
+#pragma unroll
+        for (int q = 0; q < VAL_WORDS; q++) key[q] = val_word(q, spat[Ac[i]], Ax, b, len);
+        // -1 / 0 / 1: entry c below / equal to / above the key
+        auto cmp = [&](int c) {
+            int r = 0;
+#pragma unroll
+            for (int q = VAL_WORDS - 1; q >= 0; q--) {
+                const pat_t w = sv[q][c];
+                if (w != key[q]) r = w < key[q] ? -1 : 1;
+            }
+            return r;
+        };
+        int lo = 0, hi = nv - 1;
+        while (lo < hi) {
+            int mid = (lo + hi) >> 1;
+            if (cmp(mid) < 0)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if (cmp(lo) != 0) atomicOr(bad, 1);
+        Av[i] = (uint8_t)lo;
+    }
+}
+
 // build_windows' first test (capi.cpp): does some WIN_ROWS-row block's column
 // span exceed WIN_CAP?  One workgroup per block
 __global__ __launch_bounds__(CT) void k_win_wide(long nb, int nrows, const int *__restrict__ Ap,
@@ -864,6 +1007,91 @@ int lssp_amd::build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
     }
     M->aux_bytes += (long long)ac_bytes + (long long)sizeof(pat_t) * (long long)pat.size();
     M->npat = (int)pat.size();
+    return LSSP_AMD_OK;
+}
+
+// The value codes of a row-coded matrix, from its resident Ap, Ac and Ax: one
+// routine for the upload, mat_from_device and every lssp_amd_mat_update_values,
+// which first drops what an earlier call built.  The value rows are numbered
+// by ascending key, whatever order the rows arrived in.
+int lssp_amd::build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
+{
+    // per value row: its key, and its decoded pattern (d_voff)
+    constexpr long long ROW_BYTES = sizeof(pat_t) * VAL_WORDS + sizeof(int) * (ROWPAT_LEN + 1);
+    auto drop = [M]() {
+        if (M->Av) (void)hipFree(M->Av);
+        if (M->d_val) (void)hipFree(M->d_val);
+        if (M->d_voff) (void)hipFree(M->d_voff);
+        M->Av = nullptr;
+        M->d_val = nullptr;
+        M->d_voff = nullptr;
+    };
+    if (M->nval > 0) M->aux_bytes -= (long long)M->nrows + 32 + ROW_BYTES * M->nval;
+    M->nval = 0;
+    drop();
+    if (M->npat == 0 || !M->Ac || M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(gk, pat_t, PAT_HS + ROWPAT_MAX);
+    SCRATCH(gi, int, 2);
+    SCRATCH(rep, int, ROWVAL_MAX);
+    SCRATCH(keys, pat_t, VAL_WORDS * ROWVAL_MAX);
+    SCRATCH(bad, int, 1);
+    k_pat_init<<<1, CT, 0, s>>>(gk, gi);
+    k_val_collect<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ac, M->Ax, gk, gi, rep);
+    LSSP_HIP(hipGetLastError());
+    int head[2];  // count, flag
+    LSSP_HIP(hipMemcpyAsync(head, gi, sizeof(head), hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipStreamSynchronize(s));
+    if (head[P_OVER] || head[P_COUNT] > ROWVAL_MAX || head[P_COUNT] <= 0) return LSSP_AMD_OK;  // not value-coded
+    const int nv = head[P_COUNT];
+    k_val_gather<<<1, CT, 0, s>>>(nv, rep, M->Ap, M->Ac, M->Ax, M->d_pat, keys);
+    LSSP_HIP(hipGetLastError());
+    typedef std::array<pat_t, VAL_WORDS> key_t;
+    std::vector<key_t> key(nv);
+    LSSP_HIP(hipMemcpyAsync(key.data(), keys, sizeof(key_t) * nv, hipMemcpyDeviceToHost, s));
+    LSSP_HIP(hipStreamSynchronize(s));
+    std::sort(key.begin(), key.end());  // by pattern key (= by pattern code), then by the value bits in order
+    std::vector<pat_t> tab((size_t)VAL_WORDS * nv);
+    for (int q = 0; q < VAL_WORDS; q++)
+        for (int t = 0; t < nv; t++) tab[(size_t)q * nv + t] = key[t][q];
+    // +32: padded as Ac is
+    const size_t av_bytes = (size_t)M->nrows + 32;
+    LSSP_HIP(hipMalloc(&M->Av, av_bytes));
+    LSSP_HIP(hipMalloc(&M->d_val, sizeof(pat_t) * tab.size()));
+    LSSP_HIP(hipMemsetAsync(M->Av + M->nrows, 0, 32, s));
+    LSSP_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    LSSP_HIP(hipMemcpyAsync(M->d_val, tab.data(), sizeof(pat_t) * tab.size(), hipMemcpyHostToDevice, s));
+    k_val_codes<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ac, M->Ax, M->d_pat, M->npat, M->d_val, nv,
+                                                  M->Av, bad);
+    LSSP_HIP(hipGetLastError());
+    int hbad = 0;
+    TRY(fetch(s, bad, &hbad));
+    if (hbad) {  // two distinct rows shared a mix: the table lacks one of them
+        drop();
+        return LSSP_AMD_OK;
+    }
+    // the patterns decoded for the kernel
+    std::vector<int> off(M->ndiag), voff((size_t)(ROWPAT_LEN + 1) * nv);
+    LSSP_HIP(hipMemcpy(off.data(), M->d_off, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
+    for (int t = 0; t < nv; t++) {
+        const pat_t pt = key[t][0];
+        int len = 0;
+        while (len < ROWPAT_LEN && ((pt >> (8 * len)) & 255u) != 0) len++;
+        for (int k = 0; k < ROWPAT_LEN; k++)
+            voff[(size_t)k * nv + t] = len ? off[(int)((pt >> (8 * std::min(k, len - 1))) & 255u) - 1] : 0;
+        voff[(size_t)ROWPAT_LEN * nv + t] = len;
+    }
+    LSSP_HIP(hipMalloc(&M->d_voff, sizeof(int) * voff.size()));
+    LSSP_HIP(hipMemcpy(M->d_voff, voff.data(), sizeof(int) * voff.size(), hipMemcpyHostToDevice));
+    // as pat_thr: the sorted keys' lengths ascend
+    for (int l = 0; l < ROWPAT_LEN; l++) {
+        int shorter = 0;
+        for (const key_t &k : key) shorter += (k[0] >> (8 * l)) == 0;  // at most l entries
+        M->val_thr[l] = (unsigned short)shorter;
+    }
+    M->aux_bytes += (long long)av_bytes + ROW_BYTES * nv;
+    M->nval = nv;
     return LSSP_AMD_OK;
 }
 
@@ -1229,7 +1457,8 @@ static int diag_ids_dev(lssp_amd_ctx *c, lssp_amd_mat *M)
     M->max_off = 0;
     for (int o : off) M->max_off = std::max(M->max_off, std::abs(o));
     M->max_off_int = M->max_off;
-    return lssp_amd::build_row_codes(c, M);
+    TRY(lssp_amd::build_row_codes(c, M));
+    return lssp_amd::build_val_codes(c, M);
 }
 
 // build_windows (capi.cpp) for a CSR in HBM: the span test runs on the device;
@@ -1307,8 +1536,9 @@ int lssp_amd_mat_from_device(lssp_amd_ctx *c, int nrows, int ncols, int nnz, con
     return LSSP_AMD_OK;
 }
 
-// New values on the same pattern.  The offset ids, the window spans and the
-// sliced copy's columns and row order depend on the pattern alone: the values
+// New values on the same pattern.  The offset ids, the row codes, the window
+// spans and the sliced copy's columns and row order depend on the pattern
+// alone; the value codes do not and are built again (build_val_codes).  The values
 // are copied into the resident Ax and, for a windowed matrix, into the sliced
 // copy's value slots (k_sell_refill); its padding slots stay +0.0.
 int lssp_amd_mat_update_values(lssp_amd_ctx *c, lssp_amd_mat *A, const double *dAx, int nnz)
@@ -1326,7 +1556,8 @@ int lssp_amd_mat_update_values(lssp_amd_ctx *c, lssp_amd_mat *A, const double *d
         LSSP_HIP(hipGetLastError());
     }
     LSSP_HIP(hipStreamSynchronize(s));
-    return LSSP_AMD_OK;
+    // the value codes describe the old values: rebuilt for the new ones, or dropped
+    return lssp_amd::build_val_codes(c, A);
 }
 
 }  // extern "C"

@@ -132,6 +132,25 @@ struct lssp_amd_mat {
     unsigned long long *d_pat = nullptr;
     int npat = 0;
     unsigned short pat_thr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // value coding (SpMV): when a row-coded matrix has at most ROWVAL_MAX
+    // distinct rows -- pattern code plus the bit patterns of the row's values
+    // in CSR order (a constant-coefficient 7-pt grid has 27) -- Av[i] indexes
+    // the table d_val and the SpMV reads one byte per row and no Ax.  d_val
+    // holds 9 rows of nval 64-bit words: word c of row 0 = the pattern key of
+    // value row c (as in d_pat), of row 1 + k = the bits of its value k (+0.0
+    // past its length).  The value rows are numbered by ascending (pattern
+    // code, value bits in order), so lengths still ascend with the code and
+    // val_thr is pat_thr's counterpart (build_val_codes, convert.hip, which
+    // compares every row bit for bit with the table row it assigns).  d_voff
+    // is the table's patterns decoded for the kernel, 9 rows of nval ints:
+    // word c of row k = the column offset of value row c's entry k (past its
+    // length: of its last entry again; an empty row's: 0), of row 8 = its
+    // length.  nval == 0: not value-coded
+    uint8_t *Av = nullptr;
+    unsigned long long *d_val = nullptr;
+    int *d_voff = nullptr;
+    int nval = 0;
+    unsigned short val_thr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // max |col - row| over the rows of the halo-free chunks [ich0, ich1) of a
     // distributed matrix (its whole row range on one rank: max_off)
     int max_off_int = 0;
@@ -150,7 +169,7 @@ struct lssp_amd_mat {
     double *s_ax = nullptr;
     uint32_t *s_col = nullptr, *s_row = nullptr;
     int *s_meta = nullptr;
-    // device bytes held beside the CSR arrays (offset ids + table, row codes + table, window spans,
+    // device bytes held beside the CSR arrays (offset ids + table, row codes + table, value codes + table, window spans,
     // the sliced copy): lssp_amd_mat_bytes
     long long aux_bytes = 0;
     // k_spmv3's block streams, timed at upload (tune_spmv_streams); 0: the default 8
@@ -371,6 +390,11 @@ constexpr int DIAG_MAX = 255, DIAG_HS = 1024;
 // at most ROWPAT_MAX patterns of at most ROWPAT_LEN entries, else npat stays 0
 constexpr int ROWPAT_MAX = 256, ROWPAT_LEN = 8;
 int build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M);
+// value coding of a row-coded matrix from its resident Ap / Ac / Ax
+// (convert.hip): at most ROWVAL_MAX distinct rows, else nval stays 0.  It
+// first drops the codes the matrix has (lssp_amd_mat_update_values calls it again)
+constexpr int ROWVAL_MAX = 256;
+int build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M);
 int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, const double *x,
                 double beta, const double *y, double *z, int nred, const double *w0,
                 const double *w1, long cb = 0, long ce = -1);  // chunks [cb, ce); ce < 0: all

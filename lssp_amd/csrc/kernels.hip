@@ -369,6 +369,12 @@ struct SpmvArgs {
     const unsigned long long *pat;
     int npat;
     unsigned short thr[8];
+    // value coding (lssp_amd_mat::Av, d_val, nval, val_thr), COL_VAL kernels; nval == 0: not used
+    // and its decoded form (lssp_amd_mat::d_voff); v8: some row has 8 entries
+    const uint8_t *Av;
+    const unsigned long long *val;
+    const int *voff;
+    int nval, v8;
 };
 
 // The 256-row blocks are dealt so that each of the 8 XCDs owns one contiguous
@@ -390,23 +396,143 @@ struct SpmvArgs {
 // from a scan of the block's lengths -- a wave scan, the wave totals handed
 // through LDS across the staging barrier -- onto Ap[r0]; only Ax is staged,
 // and every row has at most 8 entries, so a block always fits SPMV_CAP.
-enum { COL_J = 0, COL_ID = 1, COL_ROW = 2 };
+// COL_VAL takes the values too from the row's code (lssp_amd_mat::Av: a table
+// of the matrix's distinct rows, pattern key and 8 values each, of which the
+// workgroup copies the nval live entries to LDS): 1 byte per row and neither
+// Ap nor Ax, so no staging, no scan, and one barrier, behind the table copy.
+// With the value stream gone the kernel is paced by the instructions it issues
+// per entry, so the table is read in its decoded form (lssp_amd_mat::d_voff:
+// a column offset per entry and the row's length) and not through thr / off.
+// A workgroup walks SPMV_VB consecutive blocks of its stream with that one
+// copy: the codes and dot operands of all of them are loaded up front, then
+// all their x gathers are issued, then each block runs its own epilogue and
+// writes its own rows and chunk partial, as a workgroup of its own would.
+enum { COL_J = 0, COL_ID = 1, COL_ROW = 2, COL_VAL = 3 };
+#ifndef LSSP_AMD_SPMV_VB
+#define LSSP_AMD_SPMV_VB 4
+#endif
+constexpr int SPMV_VB = LSSP_AMD_SPMV_VB;
 template <int EPI, int NRED, int CM>
 __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
 {
-    constexpr bool CMP = CM == COL_ID, ROW = CM == COL_ROW;
+    constexpr bool CMP = CM == COL_ID, ROW = CM == COL_ROW, VAL = CM == COL_VAL;
     static_assert(256 * 8 <= SPMV_CAP, "a row-coded block fits the staging buffer");
     constexpr int NX2 = (SPMV_CAP / 2 + 1 + 255) / 256;  // double2 loads per lane
     constexpr int NJ4 = CMP ? 1 : (SPMV_CAP / 4 + 1 + 255) / 256;  // int4 loads per lane (16 ids when CMP)
-    __shared__ __attribute__((aligned(16))) double sx[SPMV_CAP + 2];
-    __shared__ __attribute__((aligned(16))) int sj[ROW ? 1 : CMP ? SPMV_CAP / 4 + 8 : SPMV_CAP + 4];
-    __shared__ int soff[CM != COL_J ? 256 : 1];
+    __shared__ __attribute__((aligned(16))) double sx[VAL ? 2 : SPMV_CAP + 2];
+    __shared__ __attribute__((aligned(16))) int sj[ROW || VAL ? 1 : CMP ? SPMV_CAP / 4 + 8 : SPMV_CAP + 4];
+    __shared__ int soff[CMP || ROW ? 256 : 1];
     __shared__ unsigned long long spat[ROW ? 256 : 1];
+    __shared__ double sval[VAL ? ROWPAT_LEN : 1][VAL ? ROWVAL_MAX : 1];
+    __shared__ int svoff[VAL ? ROWPAT_LEN + 1 : 1][VAL ? ROWVAL_MAX : 1];
     __shared__ int swt[ROW ? 4 : 1];  // the waves' entry counts
     __shared__ double lds[MAX_SLOTS][4];
     // the guard is read with the row bounds and tested before the entries are
     // loaded: its round trip overlaps theirs instead of preceding it
     const double gv = a.guard ? *a.guard : 0.0;
+    if constexpr (VAL) {
+        const int tid = threadIdx.x;
+        const long per = (nblk + a.streams - 1) / a.streams;  // blocks per stream
+        const long pos0 = (long)(blockIdx.x / a.streams) * SPMV_VB;
+        const long lb0 = (blockIdx.x % a.streams) * per + pos0;
+        if (pos0 >= per || lb0 >= nblk) return;
+        long blk[SPMV_VB];
+        bool live[SPMV_VB];
+        unsigned code[SPMV_VB];
+        double w0p[SPMV_VB], w1p[SPMV_VB], sum[SPMV_VB];
+#pragma unroll
+        for (int j = 0; j < SPMV_VB; j++) {
+            long lb = lb0 + j;
+            live[j] = pos0 + j < per && lb < nblk;  // the same for every lane
+            if (!live[j]) lb = lb0;
+            if (a.pbpp > 0 && lb < (long)a.pbpp * a.pz) {  // (32-bit: the grouped blocks are fewer than 2^31)
+                const unsigned ub = (unsigned)lb, gs = (unsigned)(a.pw * a.pz), g = ub / gs, rem = ub - g * gs;
+                lb = (long)((rem / a.pw) * a.pbpp + g * a.pw + rem % a.pw);
+            }
+            blk[j] = a.blk0 + lb;
+            const int rr = min((int)(blk[j] * 256) + tid, a.nrows - 1);
+            code[j] = __builtin_nontemporal_load(a.Av + rr);
+            w0p[j] = w1p[j] = 0.0;
+            if (NRED > 0) {  // as below
+                if (a.ntv) {
+                    if (a.w0 != a.z) w0p[j] = __builtin_nontemporal_load(a.w0 + rr);
+                    if (NRED > 1 && a.w1 && a.w1 != a.z) w1p[j] = __builtin_nontemporal_load(a.w1 + rr);
+                } else {
+                    if (a.w0 != a.z) w0p[j] = a.w0[rr];
+                    if (NRED > 1 && a.w1 && a.w1 != a.z) w1p[j] = a.w1[rr];
+                }
+            }
+        }
+        // the table's values (rows 1 .. 8 of d_val) and the decoded patterns: entry c's
+        // column offsets in rows 0 .. 7 of d_voff, its length in row 8
+        for (int t = tid; t < (ROWPAT_LEN + 1) * a.nval; t += 256) {
+            const int q = t / a.nval, c = t - q * a.nval;
+            svoff[q][c] = a.voff[t];
+            if (q < ROWPAT_LEN) sval[q][c] = __longlong_as_double((long long)a.val[a.nval + t]);
+        }
+        if (gv != 0.0) return;
+        __syncthreads();
+        // every x gather of every block is issued before the first product, with no
+        // branch on the row's length around them: the table repeats a row's last
+        // offset past its length (an empty row's are 0 and read x[0]), a lane past
+        // the matrix's last row gathers for that row, and entry 7 is skipped
+        // unless some row of the matrix has 8 entries
+        int len[SPMV_VB];
+        double xv[SPMV_VB][8];
+#pragma unroll
+        for (int j = 0; j < SPMV_VB; j++) {
+            const int r = (int)(blk[j] * 256) + tid;
+            const int lt = svoff[ROWPAT_LEN][code[j]];
+            const double *xb = a.x + (lt > 0 ? min(r, a.nrows - 1) : 0);
+            len[j] = r < a.nrows && live[j] ? lt : 0;
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                xv[j][u] = 0.0;
+                if (u == 7 && !a.v8) continue;
+                xv[j][u] = xb[svoff[u][code[j]]];
+            }
+        }
+        // the products, added in CSR order.  An entry past the row's length adds
+        // +0.0 instead of its product, which leaves the sum's bits as they are: a
+        // sum that starts at +0.0 is never -0.0 (no branch per entry)
+#pragma unroll
+        for (int j = 0; j < SPMV_VB; j++) {
+            sum[j] = 0;
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                if (u == 7 && !a.v8) continue;
+                const double pr = xv[j][u] * sval[u][code[j]];
+                sum[j] += u < len[j] ? pr : 0.0;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SPMV_VB; j++) {
+            if (!live[j]) continue;
+            const int r = (int)(blk[j] * 256) + tid;
+            double zv = 0;
+            if (r < a.nrows) {
+                if (EPI == EPI_MXY) zv = sum[j];
+                else if (EPI == EPI_AMXY) zv = sum[j] * a.alpha;
+                else if (EPI == EPI_AXPBY) zv = a.y[r] * a.beta + a.alpha * sum[j];
+                else zv = a.alpha * sum[j];
+                if (a.ntv) __builtin_nontemporal_store(zv, a.z + r);
+                else a.z[r] = zv;
+            }
+            if (NRED > 0) {
+                double v[NRED > 0 ? NRED : 1];
+                if (r < a.nrows) {
+                    v[0] = zv * (a.w0 == a.z ? zv : w0p[j]);
+                    if (NRED > 1) v[NRED > 1 ? 1 : 0] = zv * (a.w1 && a.w1 != a.z ? w1p[j] : zv);
+                    if (NRED > 2) v[NRED > 2 ? 2 : 0] = w0p[j] * w0p[j];  // (launch_spmv: w0 != z)
+                } else {
+#pragma unroll
+                    for (int q = 0; q < NRED; q++) v[q] = 0.0;
+                }
+                chunk_reduce<NRED>(v, a.part, a.pcap, blk[j], lds);
+            }
+        }
+        return;
+    }
     const long per = gridDim.x / a.streams;
     long lb = (blockIdx.x % a.streams) * per + blockIdx.x / a.streams;
     if (lb >= nblk) return;
@@ -812,6 +938,16 @@ static int spmv_rowcode()
     }();
     return k;
 }
+// LSSP_AMD_SPMV_VALCODE=0: a value-coded matrix's product reads Ax (COL_ROW)
+// all the same (tests, A/B runs); LSSP_AMD_SPMV_ROWCODE=0 implies it
+static int spmv_valcode()
+{
+    static const int k = [] {
+        const char *e = getenv("LSSP_AMD_SPMV_VALCODE");
+        return e ? atoi(e) : 1;
+    }();
+    return k;
+}
 static int spmv_streams(const lssp_amd_mat *A)
 {
     const int e = spmv_streams_env();
@@ -821,7 +957,9 @@ static int spmv_streams(const lssp_amd_mat *A)
 template <int EPI, int CM>
 static void spmv_dispatch(const SpmvArgs &a, int nred, long nblocks, hipStream_t s, long nnz_pad)
 {
-    const long g = (nblocks + a.streams - 1) / a.streams * a.streams;  // a multiple of K: whole stream shares
+    long per = (nblocks + a.streams - 1) / a.streams;                    // blocks per stream
+    if (CM == COL_VAL) per = (per + SPMV_VB - 1) / SPMV_VB;               // workgroups per stream
+    const long g = per * a.streams;                                      // a multiple of K: whole stream shares
     if (nred == 0) k_spmv3<EPI, 0, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
     else if (nred == 1) k_spmv3<EPI, 1, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
     else if (nred == 2 || EPI != EPI_AMX) k_spmv3<EPI, 2, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
@@ -831,7 +969,8 @@ static void spmv_dispatch(const SpmvArgs &a, int nred, long nblocks, hipStream_t
 template <int EPI>
 static void spmv_dispatch(const SpmvArgs &a, int nred, long nblocks, hipStream_t s, long nnz_pad)
 {
-    if (a.npat > 0) spmv_dispatch<EPI, COL_ROW>(a, nred, nblocks, s, nnz_pad);
+    if (a.nval > 0) spmv_dispatch<EPI, COL_VAL>(a, nred, nblocks, s, nnz_pad);
+    else if (a.npat > 0) spmv_dispatch<EPI, COL_ROW>(a, nred, nblocks, s, nnz_pad);
     else if (a.ndiag > 0) spmv_dispatch<EPI, COL_ID>(a, nred, nblocks, s, nnz_pad);
     else spmv_dispatch<EPI, COL_J>(a, nred, nblocks, s, nnz_pad);
 }
@@ -852,12 +991,19 @@ int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, c
     if (nb == 0) return LSSP_AMD_OK;
     SpmvArgs a{A->nrows, A->Ap, A->Aj, A->Ax, x, y, z, alpha, beta, w0, w1, c->d_part, c->part_cap,
                A->Ad, A->d_off, A->ndiag, c->guard, cb, spmv_streams(A), 0, 0, 0, spmv_ntv(),
-               nullptr, nullptr, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
+               nullptr, nullptr, 0, {0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, nullptr, 0, 0};
     if (A->npat > 0 && spmv_rowcode()) {
         a.Ac = A->Ac;
         a.pat = A->d_pat;
         a.npat = A->npat;
         memcpy(a.thr, A->pat_thr, sizeof(a.thr));
+        if (A->nval > 0 && spmv_valcode()) {
+            a.Av = A->Av;
+            a.val = A->d_val;
+            a.voff = A->d_voff;
+            a.nval = A->nval;
+            a.v8 = A->val_thr[7] < A->nval;
+        }
     }
     const long plane = A->max_off_int;
     if (A->ndiag > 0 && plane >= 256 * 8 && plane % 256 == 0) {

@@ -254,6 +254,14 @@ class DMat:
         return v.value
 
     @property
+    def valcodes(self) -> int:
+        """> 0: the SpMV reads one value-row byte per row (that many distinct rows: pattern and
+        values, bit for bit) and no matrix values"""
+        v = ctypes.c_int()
+        _ck(self.dev.L.lssp_amd_mat_valcodes(self.h, ctypes.byref(v)), "mat_valcodes")
+        return v.value
+
+    @property
     def windowed(self) -> bool:
         """the SpMV stages each 1024-row block's x span in LDS (k_spmv_win)"""
         v, w = ctypes.c_int(), ctypes.c_int()
@@ -269,7 +277,8 @@ class DMat:
 
     def update_values(self, ax: DVec):
         """New values (a device vector of nnz entries, in the handle's entry order) on the
-        same pattern: lssp_amd_mat_update_values.  Every layout is kept."""
+        same pattern: lssp_amd_mat_update_values.  Every layout is kept; the value codes
+        (valcodes) are rebuilt for the new values, or dropped."""
         _ck(self.dev.L.lssp_amd_mat_update_values(self.dev.h, self.h, ax.ptr, ax.n), "mat_update_values")
 
     def close(self):
