@@ -1,13 +1,18 @@
-// solvers.cpp -- BiCGSTAB, GMRES(m) and CG on device-resident vectors.
+// solvers.cpp -- the Krylov drivers on device-resident vectors: BiCGSTAB and
+// CG, the GMRES family (GMRES(m) left and right preconditioned, LGMRES(m, k)
+// and its right-preconditioned form, over the shared Arnoldi cycle core Gm),
+// and the drivers the reference writes as plain sequences of its L1 calls
+// (over L1K).
 //
 // Each driver replays the reference's scalar recurrences, guards, defaults and
 // iteration counting step for step (solver-bicgstab.cxx:10-175,
-// solver-gmres.cxx:12-255, solver-cg.cxx:8-136).  The inline host loops of the
-// reference become fused elementwise passes (kernels.hip, EwKind); every dot
-// or norm becomes a reduction whose finalize program updates the scalar
-// recurrence on the device, so an iteration runs without host round trips
-// and the host synchronises once per iteration (once per Arnoldi step in
-// GMRES) to test convergence, exactly where the reference branches.
+// solver-gmres.cxx:12-479, solver-lgmres.cxx:12-604, solver-cg.cxx:8-136).  The
+// inline host loops of the reference become fused elementwise passes
+// (kernels.hip, EwKind); every dot or norm becomes a reduction whose finalize
+// program updates the scalar recurrence on the device, so an iteration runs
+// without host round trips and the host synchronises once per iteration (once
+// per Arnoldi step in the GMRES family) to test convergence, exactly where the
+// reference branches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -689,334 +694,350 @@ int cg(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *
     return LSSP_AMD_OK;
 }
 
-// ---------------------------------------------------------------------------
-// GMRES(m), left preconditioned, MGS Arnoldi, Givens on the host
-// (solver-gmres.cxx:12-255)
-// ---------------------------------------------------------------------------
-int gmres(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *nits, double *res_out)
-{
+// ===========================================================================
+// The GMRES family: gmres, gmres_r, lgmres and lgmres_r restate their reference
+// drivers call for call (solver-gmres.cxx, solver-lgmres.cxx).  What the four
+// have in common, token for token, is in Gm: the parameter defaults, limits,
+// header lines and work storage (setup), the start up to the stop scale
+// (start), one Hessenberg column by MGS (column), its Givens rotation
+// (rotate), the back substitution (solve), the staging of ym and the footer
+// lines.  What differs stays in the drivers: how v_0 and the next basis vector
+// are formed, the side of the preconditioner, the stop tests inside and after
+// a cycle, and the x update.
+// ===========================================================================
+struct Gm {
+    Run &R;
+    const lssp_amd_solve_params &P;
+    const char *name = "";               // prefix of the header and footer lines
     const double t_start = wall_time();  // the reference driver's lssp_get_time() ("total time")
-    lssp_amd_ctx *c = R.c;
-    double tol_rel, tol_abs, tol_rb = P.tol_rb;
-    int maxit;
-    defaults(P, tol_rel, tol_abs, maxit);
-    int m = P.restart < 0 ? DEF_RESTART : P.restart;
-    if (tol_rb < 0) tol_rb = DEF_TOL;
-    if (m <= 0) return LSSP_AMD_EINVAL;
-    if (S_H + 2 * m + 2 > NSCAL) return LSSP_AMD_EUNSUPPORTED;  // Hessenberg column + ym staging
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("gmres: restart parameter m: %d\n", m);
-        lprint("gmres: maximal iteration: %d\n", maxit);
-        lprint("gmres: tolerance abs: %g\n", tol_abs);
-        lprint("gmres: tolerance rel: %g\n", tol_rel);
-        lprint("gmres: tolerance rbn: %g\n", tol_rb);
-    }
-    double *wj = R.vec(), *rg = R.vec();
-    double *V = R.vec(R.nx * (long)m);
-    double *d_ym = R.vec(m);
-    if (!wj || !rg || !V || !d_ym) return LSSP_AMD_ENOMEM;
-    auto Vi = [&](int i) { return V + (long)i * R.nx; };
-    std::vector<double> H((size_t)(m + 1) * m), gg(m + 1), cs(m), sn(m), ym(m);
-    auto HG = [&](int row, int col) -> double & { return H[(size_t)row * m + col]; };
-
-    LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));  // :85
-    LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :88
-    LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :89
-    LSSP_TRY(R.sync(0, 16));
-    const double b_norm = R.h(S_BNORM);
-    tol_rb *= b_norm;
-    double beta = R.h(S_RES);
-    int inner = 0;
-    if (beta <= tol_abs) {
-        *nits = 0;
-        *res_out = beta;
+    double tol_rel = 0, tol_abs = 0, tol_rb = 0;
+    double tol = 0, rtol = 0;  // the stop scale; tol / ||r0|| (the left-preconditioned drivers' gstol)
+    double b_norm = 0, err_rel = 0, beta = 0;
+    int maxit = 0, inner = 0;
+    int mk = 0, auk = 0, mmax = 0;  // restart m; augmentation k (0: none); a cycle's columns at most, m + k
+    double *wj = nullptr, *rg = nullptr, *V = nullptr, *Z = nullptr, *d_ym = nullptr;
+    std::vector<double> H, gg, cs, sn, ym;  // Hessenberg (mmax + 1) x mmax, its rhs, the rotations, the solution
+    Gm(Run &r, const lssp_amd_solve_params &p) : R(r), P(p) {}
+    double *Vi(int i) const { return V + (long)i * R.nx; }
+    double *Zi(int i) const { return Z + (long)i * R.nx; }
+    double &HG(int row, int col) { return H[(size_t)row * mmax + col]; }
+    // aug: LGMRES(m, k), the basis takes up to k corrections z; dev_ym: the x update reads ym on the device
+    int setup(const char *who, bool aug, bool dev_ym)
+    {
+        name = who;
+        tol_rb = P.tol_rb;
+        defaults(P, tol_rel, tol_abs, maxit);
+        mk = P.restart < 0 ? DEF_RESTART : P.restart;
+        if (aug) auk = P.aug_k <= 0 ? 3 : P.aug_k;  // lssp.cxx:6
+        if (tol_rb < 0) tol_rb = DEF_TOL;
+        if (mk <= 0) return LSSP_AMD_EINVAL;
+        mmax = mk + auk;
+        if (S_H + 2 * mmax + 2 > NSCAL) return LSSP_AMD_EUNSUPPORTED;  // Hessenberg column + ym staging
+        if (aug && (mmax > 0x7fff || auk > 0x7fff)) return LSSP_AMD_EUNSUPPORTED;  // K_LGM_X packs both in e.k
+        if (P.verb >= 2 && R.rank == 0) {
+            lprint("%s: restart parameter m: %d\n", name, mk);
+            if (aug) lprint("%s: aug k: %d\n", name, auk);
+            lprint("%s: maximal iteration: %d\n", name, maxit);
+            lprint("%s: tolerance abs: %g\n", name, tol_abs);
+            lprint("%s: tolerance rel: %g\n", name, tol_rel);
+            lprint("%s: tolerance rbn: %g\n", name, tol_rb);
+        }
+        wj = R.vec();
+        rg = R.vec();
+        V = R.vec(R.nx * (long)mmax);
+        if (aug) Z = R.vec(R.nx * (long)auk);
+        if (dev_ym) d_ym = R.vec(mmax);
+        if (!wj || !rg || !V || (aug && !Z) || (dev_ym && !d_ym)) return LSSP_AMD_ENOMEM;
+        H.assign((size_t)(mmax + 1) * mmax, 0.0);
+        gg.assign(mmax + 1, 0.0);
+        cs.assign(mmax, 0.0);
+        sn.assign(mmax, 0.0);
+        ym.assign(mmax, 0.0);  // LGMRES: ym persists across cycles and starts at zero
         return LSSP_AMD_OK;
     }
-    const double err_rel = beta;
-    double tol = tol_rel * err_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
-    const double rtol = tol / beta;
-    double gstol = 0.;
-
-    while (inner < maxit) {
-        int i, kk;
-        double gs_norm = 0.;
-        const bool first_cycle = inner == 0;
-        LSSP_TRY(R.pc(Vi(0), rg));                                             // :112-113
-        LSSP_TRY(R.dot1(Vi(0), Vi(0), R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :115
-        {
-            Ew e;
-            e.kind = K_DIVS;  // :129-131
-            e.out0 = Vi(0);
-            e.sidx = S_TMP;
-            LSSP_TRY(R.ew(e));
-        }
+    // rg = b - A x and beta = ||rg||, one host round trip
+    int residual(double *x, const double *b)
+    {
+        LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));
+        LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));
+        LSSP_TRY(R.sync(0, 16));
+        beta = R.h(S_RES);
+        return LSSP_AMD_OK;
+    }
+    // ||b||, r0 = b - A x, beta = ||r0||.  done: beta <= tol_abs, x stays as it is;
+    // else the stop scale tol = max(tol_rel ||r0||, tol_abs, tol_rb ||b||)
+    int start(double *x, const double *b, bool &done)
+    {
+        LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));
+        LSSP_TRY(residual(x, b));
+        b_norm = R.h(S_BNORM);
+        tol_rb *= b_norm;
+        done = beta <= tol_abs;
+        if (done) return LSSP_AMD_OK;
+        err_rel = beta;
+        tol = tol_rel * err_rel;
+        if (tol < tol_abs) tol = tol_abs;
+        if (tol < tol_rb) tol = tol_rb;
+        rtol = tol / beta;
+        return LSSP_AMD_OK;
+    }
+    void new_cycle()
+    {
         std::fill(gg.begin(), gg.end(), 0.0);
         std::fill(H.begin(), H.end(), 0.0);
-        bool have_beta = false;
-        for (i = 0; i < m; i++) {
-            inner++;
-            LSSP_TRY(R.spmv(EPI_MXY, 1, Vi(i), 0, nullptr, rg));  // :138
-            LSSP_TRY(R.pc(wj, rg));                                // :139-140
-            LSSP_TRY(R.dot1(wj, Vi(0), R.fin(FIN_STORE, 1, R.T(), -1, S_H)));  // :143, j = 0
-            for (int j = 0; j <= i; j++) {  // :142-147, axpy fused with the next dot / the norm
-                Ew e;
-                e.kind = K_GM_MGS;
-                e.out0 = wj;
-                e.x = Vi(j);
-                e.sidx = S_H + j;
-                e.nred = 1;
-                e.r0a = wj;
-                e.r0b = j < i ? Vi(j + 1) : wj;
-                LSSP_TRY(R.ew(e));
-                if (j < i)
-                    LSSP_TRY(R.fin1(wj, Vi(j + 1), R.fin(FIN_STORE, 1, R.T(), -1, S_H + j + 1)));
-                else
-                    LSSP_TRY(R.fin1(wj, wj, R.fin(FIN_NORM, 1, R.T(), -1, S_H + i + 1)));  // :149
-            }
-            LSSP_TRY(R.sync(0, S_H + i + 2));
-            if (!have_beta) {
-                beta = R.h(S_TMP);
-                gg[0] = beta;  // :116
-                if (first_cycle) gstol = rtol * beta * 0.5;  // :121-123
-                have_beta = true;
-            }
-            for (int j = 0; j <= i; j++) HG(j, i) = R.h(S_H + j);
-            const double hij = R.h(S_H + i + 1);
-            HG(i + 1, i) = hij;
-            if (std::fabs(hij) <= BREAKDOWN) {  // :152-155
-                i--;
-                break;
-            } else if (i + 1 < m) {
-                Ew e;
-                e.kind = K_AXY;  // :157
-                e.a = 1 / hij;
-                e.x = wj;
-                e.out0 = Vi(i + 1);
-                LSSP_TRY(R.ew(e));
-            }
-            for (int j = 0; j < i; j++) {  // :160-166
-                const double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
-                const double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
-                HG(j, i) = h1;
-                HG(j + 1, i) = h2;
-            }
-            double gma = std::sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));  // :168
-            if (std::fabs(gma) == 0.) gma = 1e-20;
-            cs[i] = HG(i, i) / gma;
-            sn[i] = HG(i + 1, i) / gma;
-            gg[i + 1] = -sn[i] * gg[i];
-            gg[i] = cs[i] * gg[i];
-            HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
-            gs_norm = std::fabs(gg[i + 1]);
-            if (gs_norm <= gstol) break;  // :179-181
+    }
+    // Column i of the Hessenberg matrix from wj = (the operator) v_i: MGS against
+    // v_0 .. v_i, each axpy fused with the next dot or with the closing norm,
+    // then the one host round trip of the step (scalars 0 .. S_H + i + 1, so
+    // S_TMP comes along).  wj is left orthogonalised, not normalised; broke:
+    // |h(i+1, i)| <= BREAKDOWN, the reference's "i--; break"
+    int column(int i, bool &broke)
+    {
+        LSSP_TRY(R.dot1(wj, Vi(0), R.fin(FIN_STORE, 1, R.T(), -1, S_H)));  // j = 0
+        for (int j = 0; j <= i; j++) {
+            Ew e;
+            e.kind = K_GM_MGS;
+            e.out0 = wj;
+            e.x = Vi(j);
+            e.sidx = S_H + j;
+            e.nred = 1;
+            e.r0a = wj;
+            e.r0b = j < i ? Vi(j + 1) : wj;
+            LSSP_TRY(R.ew(e));
+            if (j < i)
+                LSSP_TRY(R.fin1(wj, Vi(j + 1), R.fin(FIN_STORE, 1, R.T(), -1, S_H + j + 1)));
+            else
+                LSSP_TRY(R.fin1(wj, wj, R.fin(FIN_NORM, 1, R.T(), -1, S_H + i + 1)));
         }
-        if (!have_beta) {  // (i == 0 breakdown without a sync is impossible; kept for safety)
-            LSSP_TRY(R.sync(0, 16));
-            beta = R.h(S_TMP);
-            gg[0] = beta;
-            if (first_cycle) gstol = rtol * beta * 0.5;
+        LSSP_TRY(R.sync(0, S_H + i + 2));
+        for (int j = 0; j <= i; j++) HG(j, i) = R.h(S_H + j);
+        HG(i + 1, i) = R.h(S_H + i + 1);
+        broke = std::fabs(HG(i + 1, i)) <= BREAKDOWN;
+        return LSSP_AMD_OK;
+    }
+    // the earlier rotations applied to column i, the new one formed and applied
+    // to the column and to gg; returns |gg[i + 1]|, the residual estimate
+    double rotate(int i)
+    {
+        for (int j = 0; j < i; j++) {
+            const double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
+            const double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
+            HG(j, i) = h1;
+            HG(j + 1, i) = h2;
         }
-        kk = i == m ? m : i + 1;  // :185
-        for (i = kk - 1; i >= 0; i--) {  // :186-194
+        double gma = std::sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));
+        if (std::fabs(gma) == 0.) gma = 1e-20;
+        cs[i] = HG(i, i) / gma;
+        sn[i] = HG(i + 1, i) / gma;
+        gg[i + 1] = -sn[i] * gg[i];
+        gg[i] = cs[i] * gg[i];
+        HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
+        return std::fabs(gg[i + 1]);
+    }
+    // ym[0 .. kk) from the triangular system of the first kk columns
+    void solve(int kk)
+    {
+        for (int i = kk - 1; i >= 0; i--) {
             ym[i] = gg[i] / HG(i, i);
             for (int j = 0; j < i; j++) gg[j] = gg[j] - ym[i] * HG(j, i);
         }
-        if (kk > 0) {
-            memcpy(c->h_scal + NSCAL - m, ym.data(), sizeof(double) * kk);
-            LSSP_HIP(hipMemcpyAsync(d_ym, c->h_scal + NSCAL - m, sizeof(double) * kk,
-                                    hipMemcpyHostToDevice, c->stream));
+    }
+    // ym[0 .. cnt) to d_ym through the pinned tail of the host scalars
+    int ym_to_device(int cnt)
+    {
+        lssp_amd_ctx *c = R.c;
+        memcpy(c->h_scal + NSCAL - mmax, ym.data(), sizeof(double) * cnt);
+        LSSP_HIP(hipMemcpyAsync(d_ym, c->h_scal + NSCAL - mmax, sizeof(double) * cnt, hipMemcpyHostToDevice,
+                                c->stream));
+        return LSSP_AMD_OK;
+    }
+    int axy(double a, const double *src, double *dst)  // lssp_vec_axy
+    {
+        Ew e;
+        e.kind = K_AXY;
+        e.a = a;
+        e.x = src;
+        e.out0 = dst;
+        return R.ew(e);
+    }
+    int axpby(double a, const double *src, double bb, double *dst)  // lssp_vec_axpby
+    {
+        Ew e;
+        e.kind = K_AXPBY;
+        e.a = a;
+        e.b = bb;
+        e.x = src;
+        e.out0 = dst;
+        return R.ew(e);
+    }
+    int copy(const double *src, double *dst)  // lssp_vec_copy
+    {
+        Ew e;
+        e.kind = K_COPY;
+        e.x = src;
+        e.out0 = dst;
+        return R.ew(e);
+    }
+    int divs(double *v, int sidx)  // v /= the device scalar sidx: the reference's inline division loops
+    {
+        Ew e;
+        e.kind = K_DIVS;
+        e.out0 = v;
+        e.sidx = sidx;
+        return R.ew(e);
+    }
+    void footer() const
+    {
+        if (P.verb >= 2 && R.rank == 0) {
+            lprint("%s: total iteration: %d\n", name, inner);
+            lprint("%s: total time: %g\n", name, wall_time() - t_start);
         }
+    }
+    int result(int *nits, double *res_out) const
+    {
+        *nits = inner;
+        *res_out = beta;
+        return LSSP_AMD_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// GMRES(m), left preconditioned, MGS Arnoldi, Givens on the host
+// (solver-gmres.cxx:12-255).  Its own: v_0 = M^-1 rg / ||.|| by the device
+// scalar, whose norm the host reads with the first column's round trip; one
+// message line per cycle; maxit is not tested inside a cycle.
+// ---------------------------------------------------------------------------
+int gmres(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *nits, double *res_out)
+{
+    Gm G(R, P);
+    LSSP_TRY(G.setup("gmres", false, true));
+    const int m = G.mk;
+    double *const wj = G.wj, *const rg = G.rg;
+    int &inner = G.inner;
+    double &beta = G.beta;
+    bool done;
+    LSSP_TRY(G.start(x, b, done));  // :85-101
+    if (done) return G.result(nits, res_out);
+    double gstol = 0.;
+
+    while (inner < G.maxit) {
+        int i, kk;
+        double gs_norm = 0.;
+        const bool first_cycle = inner == 0;
+        LSSP_TRY(R.pc(G.Vi(0), rg));                                                 // :112-113
+        LSSP_TRY(R.dot1(G.Vi(0), G.Vi(0), R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :115
+        LSSP_TRY(G.divs(G.Vi(0), S_TMP));                                           // :129-131
+        G.new_cycle();
+        for (i = 0; i < m; i++) {
+            inner++;
+            LSSP_TRY(R.spmv(EPI_MXY, 1, G.Vi(i), 0, nullptr, rg));  // :138
+            LSSP_TRY(R.pc(wj, rg));                                  // :139-140
+            bool broke;
+            LSSP_TRY(G.column(i, broke));  // :142-149
+            if (i == 0) {  // ||v_0|| came with the first column's round trip (m >= 1: there always is one)
+                beta = R.h(S_TMP);
+                G.gg[0] = beta;  // :116
+                if (first_cycle) gstol = G.rtol * beta * 0.5;  // :121-123
+            }
+            if (broke) {  // :152-155
+                i--;
+                break;
+            } else if (i + 1 < m) {
+                LSSP_TRY(G.axy(1 / G.HG(i + 1, i), wj, G.Vi(i + 1)));  // :157
+            }
+            gs_norm = G.rotate(i);        // :160-177
+            if (gs_norm <= gstol) break;  // :179-181
+        }
+        kk = i == m ? m : i + 1;  // :185
+        G.solve(kk);              // :186-194
+        if (kk > 0) LSSP_TRY(G.ym_to_device(kk));
         {
             Ew e;
             e.kind = K_GM_X;  // :196-204
             e.out0 = x;
-            e.vbase = V;
+            e.vbase = G.V;
             e.k = kk;
-            e.u = d_ym;
+            e.u = G.d_ym;
             e.b = (double)R.nx;  // basis stride
             LSSP_TRY(R.ew(e));
         }
-        LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :206
-        LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :207
-        LSSP_TRY(R.sync(0, 16));
-        beta = R.h(S_RES);
+        LSSP_TRY(G.residual(x, b));  // :206-207
         if (P.verb >= 1 && R.rank == 0)
             lprint("gmres: itr: %4d / %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", inner, inner, beta,
-                   (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
-        if (beta <= tol) break;                                  // :215-217
-        gstol = rtol * gs_norm / (beta / err_rel) * 0.5;          // :220
+                   (G.err_rel == 0 ? 0 : beta / G.err_rel), (G.b_norm == 0 ? 0 : beta / G.b_norm));
+        if (beta <= G.tol) break;                                     // :215-217
+        gstol = G.rtol * gs_norm / (beta / G.err_rel) * 0.5;          // :220
     }
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("gmres: total iteration: %d\n", inner);
-        lprint("gmres: total time: %g\n", wall_time() - t_start);
-    }
-    *nits = inner;
-    *res_out = beta;
-    return LSSP_AMD_OK;
+    G.footer();
+    return G.result(nits, res_out);
 }
 
 // ---------------------------------------------------------------------------
 // GMRES(m), right preconditioned (solver-gmres.cxx:257-479): A M^-1 u = b,
 // x = x0 + M^-1 (V y).  The residual reported is the Givens estimate |g_{i+1}|
 // (:370, :427); a true residual b - A x is formed only to restart (:433).
+// Its own: v_0 = rg / ||rg|| by the host's 1 / beta after a round trip; one
+// message line per step (rgmres:, under gmres: header and footer lines); maxit
+// and beta <= tol are tested at every step.
 // ---------------------------------------------------------------------------
 int gmres_r(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *nits, double *res_out)
 {
-    const double t_start = wall_time();  // the reference driver's lssp_get_time() ("total time")
-    lssp_amd_ctx *c = R.c;
-    double tol_rel, tol_abs, tol_rb = P.tol_rb;
-    int maxit;
-    defaults(P, tol_rel, tol_abs, maxit);
-    int m = P.restart < 0 ? DEF_RESTART : P.restart;
-    if (tol_rb < 0) tol_rb = DEF_TOL;
-    if (m <= 0) return LSSP_AMD_EINVAL;
-    if (S_H + 2 * m + 2 > NSCAL) return LSSP_AMD_EUNSUPPORTED;
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("gmres: restart parameter m: %d\n", m);
-        lprint("gmres: maximal iteration: %d\n", maxit);
-        lprint("gmres: tolerance abs: %g\n", tol_abs);
-        lprint("gmres: tolerance rel: %g\n", tol_rel);
-        lprint("gmres: tolerance rbn: %g\n", tol_rb);
-    }
-    double *wj = R.vec(), *rg = R.vec();
-    double *V = R.vec(R.nx * (long)m);
-    double *d_ym = R.vec(m);
-    if (!wj || !rg || !V || !d_ym) return LSSP_AMD_ENOMEM;
-    auto Vi = [&](int i) { return V + (long)i * R.nx; };
-    std::vector<double> H((size_t)(m + 1) * m), gg(m + 1), cs(m), sn(m), ym(m);
-    auto HG = [&](int row, int col) -> double & { return H[(size_t)row * m + col]; };
+    Gm G(R, P);
+    LSSP_TRY(G.setup("gmres", false, true));
+    const int m = G.mk;
+    double *const wj = G.wj, *const rg = G.rg;
+    int &inner = G.inner;
+    double &beta = G.beta;
+    bool done;
+    LSSP_TRY(G.start(x, b, done));  // :324-339
+    if (done) return G.result(nits, res_out);
 
-    LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));  // :324
-    LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :327
-    LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :328
-    LSSP_TRY(R.sync(0, 16));
-    const double b_norm = R.h(S_BNORM);
-    tol_rb *= b_norm;
-    double beta = R.h(S_RES);
-    int inner = 0;
-    if (beta <= tol_abs) {  // :330-333
-        *nits = 0;
-        *res_out = beta;
-        return LSSP_AMD_OK;
-    }
-    const double err_rel = beta;
-    double tol = tol_rel * err_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
-
-    while (inner < maxit) {
+    while (inner < G.maxit) {
         int i, kk;
-        std::fill(gg.begin(), gg.end(), 0.0);  // :345-351
-        std::fill(H.begin(), H.end(), 0.0);
+        G.new_cycle();                                                    // :345-351
         LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :354
         LSSP_TRY(R.sync(0, 16));
-        gg[0] = beta = R.h(S_TMP);
-        {
-            Ew e;
-            e.kind = K_AXY;  // :355, a multiply by 1/beta
-            e.a = 1 / beta;
-            e.x = rg;
-            e.out0 = Vi(0);
-            LSSP_TRY(R.ew(e));
-        }
-        bool converged = false;
-        for (i = 0; i < m && inner < maxit; i++) {
+        G.gg[0] = beta = R.h(S_TMP);
+        LSSP_TRY(G.axy(1 / beta, rg, G.Vi(0)));  // :355, a multiply by 1/beta
+        for (i = 0; i < m && inner < G.maxit; i++) {
             inner++;
-            LSSP_TRY(R.pc(rg, Vi(i)));                              // :362-363
-            LSSP_TRY(R.spmv(EPI_MXY, 1, rg, 0, nullptr, wj));      // :364
-            LSSP_TRY(R.dot1(wj, Vi(0), R.fin(FIN_STORE, 1, R.T(), -1, S_H)));  // :367, j = 0
-            for (int j = 0; j <= i; j++) {  // :366-371, axpy fused with the next dot / the norm
-                Ew e;
-                e.kind = K_GM_MGS;
-                e.out0 = wj;
-                e.x = Vi(j);
-                e.sidx = S_H + j;
-                e.nred = 1;
-                e.r0a = wj;
-                e.r0b = j < i ? Vi(j + 1) : wj;
-                LSSP_TRY(R.ew(e));
-                if (j < i)
-                    LSSP_TRY(R.fin1(wj, Vi(j + 1), R.fin(FIN_STORE, 1, R.T(), -1, S_H + j + 1)));
-                else
-                    LSSP_TRY(R.fin1(wj, wj, R.fin(FIN_NORM, 1, R.T(), -1, S_H + i + 1)));  // :373
-            }
-            LSSP_TRY(R.sync(0, S_H + i + 2));
-            for (int j = 0; j <= i; j++) HG(j, i) = R.h(S_H + j);
-            const double hij = R.h(S_H + i + 1);
-            HG(i + 1, i) = hij;
-            if (std::fabs(hij) <= BREAKDOWN) {  // :377-380
+            LSSP_TRY(R.pc(rg, G.Vi(i)));                         // :362-363
+            LSSP_TRY(R.spmv(EPI_MXY, 1, rg, 0, nullptr, wj));    // :364
+            bool broke;
+            LSSP_TRY(G.column(i, broke));  // :366-373
+            if (broke) {                   // :377-380
                 i--;
                 break;
             } else if (i + 1 < m) {
-                Ew e;
-                e.kind = K_AXY;  // :382
-                e.a = 1 / hij;
-                e.x = wj;
-                e.out0 = Vi(i + 1);
-                LSSP_TRY(R.ew(e));
+                LSSP_TRY(G.axy(1 / G.HG(i + 1, i), wj, G.Vi(i + 1)));  // :382
             }
-            for (int j = 0; j < i; j++) {  // :385-391
-                const double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
-                const double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
-                HG(j, i) = h1;
-                HG(j + 1, i) = h2;
-            }
-            double gma = std::sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));  // :393
-            if (std::fabs(gma) == 0.) gma = 1e-20;
-            cs[i] = HG(i, i) / gma;
-            sn[i] = HG(i + 1, i) / gma;
-            gg[i + 1] = -sn[i] * gg[i];
-            gg[i] = cs[i] * gg[i];
-            HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
-            beta = std::fabs(gg[i + 1]);
+            beta = G.rotate(i);  // :385-402
             if (P.verb >= 1 && R.rank == 0)
                 lprint("rgmres: itr: %4d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", inner, beta,
-                       (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
-            if (beta <= tol) {  // :409-411 (goto solve: i is not advanced)
-                converged = true;
-                break;
-            }
+                       (G.err_rel == 0 ? 0 : beta / G.err_rel), (G.b_norm == 0 ? 0 : beta / G.b_norm));
+            if (beta <= G.tol) break;  // :409-411 (goto solve: i is not advanced)
         }
-        (void)converged;
         kk = i == m ? m : i + 1;  // :414
-        for (i = kk - 1; i >= 0; i--) {  // :415-420
-            ym[i] = gg[i] / HG(i, i);
-            for (int j = 0; j < i; j++) gg[j] = gg[j] - ym[i] * HG(j, i);
-        }
-        if (kk > 0) {  // :423-431
-            memcpy(c->h_scal + NSCAL - m, ym.data(), sizeof(double) * kk);
-            LSSP_HIP(hipMemcpyAsync(d_ym, c->h_scal + NSCAL - m, sizeof(double) * kk, hipMemcpyHostToDevice,
-                                    c->stream));
+        G.solve(kk);              // :415-420
+        if (kk > 0) {             // :423-431
+            LSSP_TRY(G.ym_to_device(kk));
             Ew e;
             e.kind = K_GMR_Z;
             e.out0 = rg;
-            e.vbase = V;
+            e.vbase = G.V;
             e.k = kk;
-            e.u = d_ym;
+            e.u = G.d_ym;
             e.b = (double)R.nx;  // basis stride
             LSSP_TRY(R.ew(e));
-            LSSP_TRY(R.pc(wj, rg));  // :429
-            Ew xa;
-            xa.kind = K_AXPBY;  // :430: x = x*1 + wj*1
-            xa.a = 1;
-            xa.b = 1;
-            xa.x = wj;
-            xa.out0 = x;
-            LSSP_TRY(R.ew(xa));
+            LSSP_TRY(R.pc(wj, rg));            // :429
+            LSSP_TRY(G.axpby(1, wj, 1, x));    // :430: x = x*1 + wj*1
         }
-        if (beta <= tol) break;                          // :433-435
+        if (beta <= G.tol) break;                        // :433-435
         LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));    // :437
     }
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("gmres: total iteration: %d\n", inner);
-        lprint("gmres: total time: %g\n", wall_time() - t_start);
-    }
+    G.footer();
     LSSP_TRY(R.sync(0, 1));  // the last x update is complete when the call returns
-    *nits = inner;
-    *res_out = beta;
-    return LSSP_AMD_OK;
+    return G.result(nits, res_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1028,172 +1049,79 @@ int gmres_r(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, 
 //   * the x update sums min(kk, m) basis terms, then -- when kk > m -- the
 //     first min(cycle, k) z terms with y[m + i] (:226-245), whether or not this
 //     cycle set them (y persists across cycles; it starts at zero here).
+// Its own beside these: the cycle's width m grows with outer, column i >= m
+// takes z_{i-m}, ||v_0|| is read at once, and all m + k entries of y go to the
+// device.  Column, rotation, back substitution: Gm, as in gmres.
 // ---------------------------------------------------------------------------
 int lgmres(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *nits, double *res_out)
 {
-    const double t_start = wall_time();  // the reference driver's lssp_get_time() ("total time")
-    lssp_amd_ctx *c = R.c;
-    double tol_rel, tol_abs, tol_rb = P.tol_rb;
-    int maxit;
-    defaults(P, tol_rel, tol_abs, maxit);
-    const int mk = P.restart < 0 ? DEF_RESTART : P.restart;
-    const int auk = P.aug_k <= 0 ? 3 : P.aug_k;  // lssp.cxx:6
-    if (tol_rb < 0) tol_rb = DEF_TOL;
-    if (mk <= 0) return LSSP_AMD_EINVAL;
-    const int mmax = mk + auk;
-    if (S_H + 2 * mmax + 2 > NSCAL || mmax > 0x7fff || auk > 0x7fff) return LSSP_AMD_EUNSUPPORTED;
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("lgmres: restart parameter m: %d\n", mk);
-        lprint("lgmres: aug k: %d\n", auk);
-        lprint("lgmres: maximal iteration: %d\n", maxit);
-        lprint("lgmres: tolerance abs: %g\n", tol_abs);
-        lprint("lgmres: tolerance rel: %g\n", tol_rel);
-        lprint("lgmres: tolerance rbn: %g\n", tol_rb);
-    }
-    double *wj = R.vec(), *rg = R.vec();
-    double *V = R.vec(R.nx * (long)mmax);
-    double *Z = R.vec(R.nx * (long)auk);
-    double *d_ym = R.vec(mmax);
-    if (!wj || !rg || !V || !Z || !d_ym) return LSSP_AMD_ENOMEM;
-    auto Vi = [&](int i) { return V + (long)i * R.nx; };
-    auto Zi = [&](int i) { return Z + (long)i * R.nx; };
-    std::vector<double> H((size_t)(mmax + 1) * mmax), gg(mmax + 1), cs(mmax), sn(mmax), ym(mmax, 0.0);
-    auto HG = [&](int row, int col) -> double & { return H[(size_t)row * mmax + col]; };
-
-    LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));  // :108
-    LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :111
-    LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :112
-    LSSP_TRY(R.sync(0, 16));
-    const double b_norm = R.h(S_BNORM);
-    tol_rb *= b_norm;
-    double beta = R.h(S_RES);
-    int inner = 0, outer = 0;
-    if (beta <= tol_abs) {
-        *nits = 0;
-        *res_out = beta;
-        return LSSP_AMD_OK;
-    }
-    const double err_rel = beta;
-    double tol = tol_rel * err_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
-    const double rtol = tol / beta;
+    Gm G(R, P);
+    LSSP_TRY(G.setup("lgmres", true, true));
+    const int mk = G.mk, auk = G.auk;
+    double *const wj = G.wj, *const rg = G.rg;
+    int &inner = G.inner;
+    double &beta = G.beta;
+    int outer = 0;
+    bool done;
+    LSSP_TRY(G.start(x, b, done));  // :108-124
+    if (done) return G.result(nits, res_out);
     double gstol = 0.;
 
-    while (inner < maxit) {
+    while (inner < G.maxit) {
         int i, kk;
         double gs_norm = 0.;
-        LSSP_TRY(R.pc(Vi(0), rg));                                             // :130-131
-        LSSP_TRY(R.dot1(Vi(0), Vi(0), R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :133
+        LSSP_TRY(R.pc(G.Vi(0), rg));                                                 // :130-131
+        LSSP_TRY(R.dot1(G.Vi(0), G.Vi(0), R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :133
         LSSP_TRY(R.sync(0, 16));
         beta = R.h(S_TMP);
         const int m = outer < auk ? mk + outer : mk + auk;  // :136-141
-        std::fill(gg.begin(), gg.end(), 0.0);
-        gg[0] = beta;
-        if (outer == 0) gstol = rtol * beta * 0.5;  // :148-150
-        std::fill(H.begin(), H.end(), 0.0);
-        {
-            Ew e;
-            e.kind = K_DIVS;  // :156-158
-            e.out0 = Vi(0);
-            e.sidx = S_TMP;
-            LSSP_TRY(R.ew(e));
-        }
+        G.new_cycle();
+        G.gg[0] = beta;
+        if (outer == 0) gstol = G.rtol * beta * 0.5;  // :148-150
+        LSSP_TRY(G.divs(G.Vi(0), S_TMP));             // :156-158
         for (i = 0; i < m; i++) {
             inner++;
-            LSSP_TRY(R.spmv(EPI_MXY, 1, i < mk ? Vi(i) : Zi(i - mk), 0, nullptr, rg));  // :165-171
-            LSSP_TRY(R.pc(wj, rg));                                                    // :173-174
-            LSSP_TRY(R.dot1(wj, Vi(0), R.fin(FIN_STORE, 1, R.T(), -1, S_H)));         // :177, j = 0
-            for (int j = 0; j <= i; j++) {  // :176-181
-                Ew e;
-                e.kind = K_GM_MGS;
-                e.out0 = wj;
-                e.x = Vi(j);
-                e.sidx = S_H + j;
-                e.nred = 1;
-                e.r0a = wj;
-                e.r0b = j < i ? Vi(j + 1) : wj;
-                LSSP_TRY(R.ew(e));
-                if (j < i)
-                    LSSP_TRY(R.fin1(wj, Vi(j + 1), R.fin(FIN_STORE, 1, R.T(), -1, S_H + j + 1)));
-                else
-                    LSSP_TRY(R.fin1(wj, wj, R.fin(FIN_NORM, 1, R.T(), -1, S_H + i + 1)));  // :183
-            }
-            LSSP_TRY(R.sync(0, S_H + i + 2));
-            for (int j = 0; j <= i; j++) HG(j, i) = R.h(S_H + j);
-            const double hij = R.h(S_H + i + 1);
-            HG(i + 1, i) = hij;
-            if (std::fabs(hij) <= BREAKDOWN) {  // :186-189
+            LSSP_TRY(R.spmv(EPI_MXY, 1, i < mk ? G.Vi(i) : G.Zi(i - mk), 0, nullptr, rg));  // :165-171
+            LSSP_TRY(R.pc(wj, rg));                                                        // :173-174
+            bool broke;
+            LSSP_TRY(G.column(i, broke));  // :176-183
+            if (broke) {                   // :186-189
                 i--;
                 break;
             } else if (i + 1 < m) {  // :191-195: v_{i+1} = w / h, a true division
-                Ew cp;
-                cp.kind = K_COPY;
-                cp.x = wj;
-                cp.out0 = Vi(i + 1);
-                LSSP_TRY(R.ew(cp));
-                Ew e;
-                e.kind = K_DIVS;
-                e.out0 = Vi(i + 1);
-                e.sidx = S_H + i + 1;
-                LSSP_TRY(R.ew(e));
+                LSSP_TRY(G.copy(wj, G.Vi(i + 1)));
+                LSSP_TRY(G.divs(G.Vi(i + 1), S_H + i + 1));
             }
-            for (int j = 0; j < i; j++) {  // :197-203
-                const double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
-                const double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
-                HG(j, i) = h1;
-                HG(j + 1, i) = h2;
-            }
-            double gma = std::sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));  // :205
-            if (std::fabs(gma) == 0.) gma = 1e-20;
-            cs[i] = HG(i, i) / gma;
-            sn[i] = HG(i + 1, i) / gma;
-            gg[i + 1] = -sn[i] * gg[i];
-            gg[i] = cs[i] * gg[i];
-            HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
-            gs_norm = std::fabs(gg[i + 1]);
+            gs_norm = G.rotate(i);        // :197-214
             if (gs_norm <= gstol) break;  // :216-218 (goto solve: i not advanced)
         }
-        kk = i;  // :221
-        for (i = kk - 1; i >= 0; i--) {  // :222-230
-            ym[i] = gg[i] / HG(i, i);
-            for (int j = 0; j < i; j++) gg[j] = gg[j] - ym[i] * HG(j, i);
-        }
-        memcpy(c->h_scal + NSCAL - mmax, ym.data(), sizeof(double) * mmax);
-        LSSP_HIP(hipMemcpyAsync(d_ym, c->h_scal + NSCAL - mmax, sizeof(double) * mmax, hipMemcpyHostToDevice,
-                                c->stream));
+        kk = i;       // :221
+        G.solve(kk);  // :222-230
+        LSSP_TRY(G.ym_to_device(G.mmax));
         {
             const int zn = outer % auk, nz = outer <= auk ? outer : auk;  // :233, :240-246
             Ew e;
             e.kind = K_LGM_X;  // :234-251
             e.out0 = x;
-            e.out1 = Zi(zn);
-            e.vbase = V;
-            e.v = Z;
-            e.u = d_ym;
+            e.out1 = G.Zi(zn);
+            e.vbase = G.V;
+            e.v = G.Z;
+            e.u = G.d_ym;
             e.sidx = mk;
             e.k = (kk & 0xffff) | (nz << 16);
             e.b = (double)R.nx;  // basis stride
             LSSP_TRY(R.ew(e));
         }
-        LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :253
-        LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :254
-        LSSP_TRY(R.sync(0, 16));
-        beta = R.h(S_RES);
+        LSSP_TRY(G.residual(x, b));  // :253-254
         if (P.verb >= 1 && R.rank == 0)
             lprint("lgmres: itr: %4d / %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", outer, inner, beta,
-                   (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
-        if (beta <= tol) break;                                  // :262
-        gstol = rtol * gs_norm / (beta / err_rel) * 0.5;          // :265
+                   (G.err_rel == 0 ? 0 : beta / G.err_rel), (G.b_norm == 0 ? 0 : beta / G.b_norm));
+        if (beta <= G.tol) break;                                     // :262
+        gstol = G.rtol * gs_norm / (beta / G.err_rel) * 0.5;          // :265
         outer++;
     }
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("lgmres: total iteration: %d\n", inner);
-        lprint("lgmres: total time: %g\n", wall_time() - t_start);
-    }
-    *nits = inner;
-    *res_out = beta;
-    return LSSP_AMD_OK;
+    G.footer();
+    return G.result(nits, res_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1209,165 +1137,69 @@ int lgmres(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, i
 //   * x += M^-1 rg, and z[outer % k] = rg (:544-548);
 //   * one iteration counter in the message lines, printed per step and once
 //     more after a cycle that did not converge (:494-498, :558-562).
+// Column, rotation and back substitution are Gm's; ym stays on the host, its
+// entries are the scalars of the update's axy / axpby chain.
 // ---------------------------------------------------------------------------
 int lgmres_r(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *nits, double *res_out)
 {
-    const double t_start = wall_time();  // the reference driver's lssp_get_time() ("total time")
-    double tol_rel, tol_abs, tol_rb = P.tol_rb;
-    int maxit;
-    defaults(P, tol_rel, tol_abs, maxit);
-    const int mk = P.restart < 0 ? DEF_RESTART : P.restart;
-    const int auk = P.aug_k <= 0 ? 3 : P.aug_k;  // lssp.cxx:6
-    if (tol_rb < 0) tol_rb = DEF_TOL;
-    if (mk <= 0) return LSSP_AMD_EINVAL;
-    const int mmax = mk + auk;
-    if (S_H + 2 * mmax + 2 > NSCAL || mmax > 0x7fff || auk > 0x7fff) return LSSP_AMD_EUNSUPPORTED;
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("lgmres: restart parameter m: %d\n", mk);
-        lprint("lgmres: aug k: %d\n", auk);
-        lprint("lgmres: maximal iteration: %d\n", maxit);
-        lprint("lgmres: tolerance abs: %g\n", tol_abs);
-        lprint("lgmres: tolerance rel: %g\n", tol_rel);
-        lprint("lgmres: tolerance rbn: %g\n", tol_rb);
-    }
-    double *wj = R.vec(), *rg = R.vec();
-    double *V = R.vec(R.nx * (long)mmax);
-    double *Z = R.vec(R.nx * (long)auk);
-    if (!wj || !rg || !V || !Z) return LSSP_AMD_ENOMEM;
-    auto Vi = [&](int i) { return V + (long)i * R.nx; };
-    auto Zi = [&](int i) { return Z + (long)i * R.nx; };
-    std::vector<double> H((size_t)(mmax + 1) * mmax), gg(mmax + 1), cs(mmax), sn(mmax), ym(mmax, 0.0);
-    auto HG = [&](int row, int col) -> double & { return H[(size_t)row * mmax + col]; };
-    auto axy = [&](double a, const double *src, double *dst) {  // lssp_vec_axy
-        Ew e;
-        e.kind = K_AXY;
-        e.a = a;
-        e.x = src;
-        e.out0 = dst;
-        return R.ew(e);
-    };
-    auto axpby = [&](double a, const double *src, double bb, double *dst) {  // lssp_vec_axpby
-        Ew e;
-        e.kind = K_AXPBY;
-        e.a = a;
-        e.b = bb;
-        e.x = src;
-        e.out0 = dst;
-        return R.ew(e);
-    };
+    Gm G(R, P);
+    LSSP_TRY(G.setup("lgmres", true, false));
+    const int mk = G.mk, auk = G.auk;
+    double *const wj = G.wj, *const rg = G.rg;
+    int &inner = G.inner;
+    double &beta = G.beta;
+    int outer = 0;
     // a z that its cycle did not set (kk == 0) reads as zero, not as a pool buffer's old contents
-    LSSP_TRY(launch_fill(R.c, Z, R.nx * (long)auk, 0));
+    LSSP_TRY(launch_fill(R.c, G.Z, R.nx * (long)auk, 0));
+    bool done;
+    LSSP_TRY(G.start(x, b, done));  // :395-410
+    if (done) return G.result(nits, res_out);
 
-    LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));  // :395
-    LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :398
-    LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :399
-    LSSP_TRY(R.sync(0, 16));
-    const double b_norm = R.h(S_BNORM);
-    tol_rb *= b_norm;
-    double beta = R.h(S_RES);
-    int inner = 0, outer = 0;
-    if (beta <= tol_abs) {  // :401-404
-        *nits = 0;
-        *res_out = beta;
-        return LSSP_AMD_OK;
-    }
-    const double err_rel = beta;
-    double tol = tol_rel * err_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
-
-    while (inner < maxit) {
+    while (inner < G.maxit) {
         int i, kk;
         const int m = outer < auk ? mk + outer : mk + auk;  // :422-427
-        std::fill(gg.begin(), gg.end(), 0.0);              // :429-435
-        std::fill(H.begin(), H.end(), 0.0);
+        G.new_cycle();                                      // :429-435
         LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_TMP)));  // :438
         LSSP_TRY(R.sync(0, 16));
-        gg[0] = beta = R.h(S_TMP);
-        LSSP_TRY(axy(1 / beta, rg, Vi(0)));  // :439
-        for (i = 0; i < m && inner < maxit; i++) {
+        G.gg[0] = beta = R.h(S_TMP);
+        LSSP_TRY(G.axy(1 / beta, rg, G.Vi(0)));  // :439
+        for (i = 0; i < m && inner < G.maxit; i++) {
             inner++;
-            LSSP_TRY(R.pc(rg, i < mk ? Vi(i) : Zi(i - mk)));        // :447-454
+            LSSP_TRY(R.pc(rg, i < mk ? G.Vi(i) : G.Zi(i - mk)));    // :447-454
             LSSP_TRY(R.spmv(EPI_MXY, 1, rg, 0, nullptr, wj));      // :456
-            LSSP_TRY(R.dot1(wj, Vi(0), R.fin(FIN_STORE, 1, R.T(), -1, S_H)));  // :458, j = 0
-            for (int j = 0; j <= i; j++) {  // :457-464, axpby fused with the next dot / the norm
-                Ew e;
-                e.kind = K_GM_MGS;
-                e.out0 = wj;
-                e.x = Vi(j);
-                e.sidx = S_H + j;
-                e.nred = 1;
-                e.r0a = wj;
-                e.r0b = j < i ? Vi(j + 1) : wj;
-                LSSP_TRY(R.ew(e));
-                if (j < i)
-                    LSSP_TRY(R.fin1(wj, Vi(j + 1), R.fin(FIN_STORE, 1, R.T(), -1, S_H + j + 1)));
-                else
-                    LSSP_TRY(R.fin1(wj, wj, R.fin(FIN_NORM, 1, R.T(), -1, S_H + i + 1)));  // :464
-            }
-            LSSP_TRY(R.sync(0, S_H + i + 2));
-            for (int j = 0; j <= i; j++) HG(j, i) = R.h(S_H + j);
-            const double hij = R.h(S_H + i + 1);
-            HG(i + 1, i) = hij;
-            if (std::fabs(hij) <= BREAKDOWN) {  // :467-470
+            bool broke;
+            LSSP_TRY(G.column(i, broke));  // :457-464
+            if (broke) {                   // :467-470
                 i--;
                 break;
             } else if (i + 1 < m) {
-                LSSP_TRY(axy(1 / hij, wj, Vi(i + 1)));  // :472
+                LSSP_TRY(G.axy(1 / G.HG(i + 1, i), wj, G.Vi(i + 1)));  // :472
             }
-            for (int j = 0; j < i; j++) {  // :475-481
-                const double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
-                const double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
-                HG(j, i) = h1;
-                HG(j + 1, i) = h2;
-            }
-            double gma = std::sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));  // :483
-            if (std::fabs(gma) == 0.) gma = 1e-20;
-            cs[i] = HG(i, i) / gma;
-            sn[i] = HG(i + 1, i) / gma;
-            gg[i + 1] = -sn[i] * gg[i];
-            gg[i] = cs[i] * gg[i];
-            HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
-            beta = std::fabs(gg[i + 1]);
+            beta = G.rotate(i);  // :475-492
             if (P.verb >= 1 && R.rank == 0)
                 lprint("lgmres: itr: %4d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", inner, beta,
-                       (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
-            if (beta <= tol) break;  // :500-502 (goto solve: i is not advanced)
+                       (G.err_rel == 0 ? 0 : beta / G.err_rel), (G.b_norm == 0 ? 0 : beta / G.b_norm));
+            if (beta <= G.tol) break;  // :500-502 (goto solve: i is not advanced)
         }
-        kk = i;  // :506
-        for (i = kk - 1; i >= 0; i--) {  // :507-512
-            ym[i] = gg[i] / HG(i, i);
-            for (int j = 0; j < i; j++) gg[j] = gg[j] - ym[i] * HG(j, i);
-        }
+        kk = i;        // :506
+        G.solve(kk);   // :507-512
         if (kk > 0) {  // :515-549; i == -1 here, so :516 always takes the basis-only sum
-            LSSP_TRY(axy(ym[0], Vi(0), rg));
-            for (i = 1; i < kk; i++) LSSP_TRY(axpby(ym[i], Vi(i), 1, rg));
-            LSSP_TRY(R.pc(wj, rg));         // :544
-            LSSP_TRY(axpby(1, wj, 1, x));   // :545
-            Ew cp;
-            cp.kind = K_COPY;  // :548
-            cp.x = rg;
-            cp.out0 = Zi(outer % auk);
-            LSSP_TRY(R.ew(cp));
+            LSSP_TRY(G.axy(G.ym[0], G.Vi(0), rg));
+            for (i = 1; i < kk; i++) LSSP_TRY(G.axpby(G.ym[i], G.Vi(i), 1, rg));
+            LSSP_TRY(R.pc(wj, rg));           // :544
+            LSSP_TRY(G.axpby(1, wj, 1, x));   // :545
+            LSSP_TRY(G.copy(rg, G.Zi(outer % auk)));  // :548
         }
-        if (beta <= tol) break;                                           // :551-553
-        LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, rg));                     // :555
-        LSSP_TRY(R.dot1(rg, rg, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));  // :556
-        LSSP_TRY(R.sync(0, 16));
-        beta = R.h(S_RES);
+        if (beta <= G.tol) break;    // :551-553
+        LSSP_TRY(G.residual(x, b));  // :555-556
         if (P.verb >= 1 && R.rank == 0)
             lprint("lgmres: itr: %4d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", inner, beta,
-                   (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
+                   (G.err_rel == 0 ? 0 : beta / G.err_rel), (G.b_norm == 0 ? 0 : beta / G.b_norm));
         outer++;
     }
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("lgmres: total iteration: %d\n", inner);
-        lprint("lgmres: total time: %g\n", wall_time() - t_start);
-    }
+    G.footer();
     LSSP_TRY(R.sync(0, 1));  // the last x update is complete when the call returns
-    *nits = inner;
-    *res_out = beta;
-    return LSSP_AMD_OK;
+    return G.result(nits, res_out);
 }
 
 
