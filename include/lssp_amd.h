@@ -371,9 +371,9 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      >= 1, block-Jacobi, BILUK, general and small 2-D factors), and the
  *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
  *      only when the PATTERN is new: new values on the same pattern stay on the
- *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor for the
- *      handles it serves and lssp_amd_bilu_refactor for packet-swept BILUK
- *      handles, below). */
+ *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor /
+ *      lssp_amd_iluk_refactor for the ILUK handles they serve and
+ *      lssp_amd_bilu_refactor for packet-swept BILUK handles, below). */
 /* lssp_mat_csr_is_sorted (matrix-utils.cxx:249-279): *sorted = 0 iff some row
  * holds neighbours Aj[k-1] > Aj[k] (equal neighbours are sorted); nnz == 0: 1.
  * Column values are compared only, never used as indices. */
@@ -485,6 +485,49 @@ int lssp_amd_ilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat
  * a handle that is never refactored allocates none of it.  A HIP error
  * part-way returns LSSP_AMD_EHIP, after which M may only be destroyed. */
 int lssp_amd_bilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat *A);
+/* The same for any one-block ILUK handle: factor M again from the values A
+ * holds now, keeping every schedule; no matrix or factor array crosses the
+ * host (one flag word is read back).  Afterwards lssp_amd_ilu_apply /
+ * _apply_async + _check / _trisolve / lssp_amd_solve with M and
+ * lssp_amd_ilu_get_factors are bitwise those of a fresh
+ * lssp_amd_ilu_create(ILUK, M's level) on the new values; lssp_amd_ilu_info and
+ * _sweep_layout answer as before.  The host copies of the factor values are
+ * refreshed by the next call that reads them (one download), and the arrays a
+ * single sweep (lssp_amd_ilu_trisolve) built are dropped and rebuilt by the
+ * next one.  All work is enqueued on the context's stream, after any earlier
+ * lssp_amd_ilu_apply_async; the call returns when the stream has finished.
+ * A superset of lssp_amd_ilu_refactor: a handle eligible there (one made by
+ * lssp_amd_ilu_create_dev included) takes that path unchanged, so one call
+ * serves every ILUK handle.  Newly eligible: M from lssp_amd_ilu_create with
+ * kind ILUK, any level (negative: the default 1), one block (blk <= 0 or >= n),
+ * whose sweeps run either on packet schedules (lssp_amd_ilu_sweep_layout: *line
+ * == 0; general patterns, ILU(k >= 2) of stencils, boxes with holes) or on the
+ * skewed ILU(1) line sweeps of a 7-point box (*line == 2 with 16 x 8 tiles: the
+ * reference's default configuration).  ILUT (its pattern depends on the
+ * values), block-Jacobi, from_factors / from_ldu and BILUK handles, the
+ * one-workgroup sweeps of a small 2-D grid (*lines == ny), a factor on the
+ * sync-free fallback (a strict row longer than 24 entries), a handle whose
+ * single-sweep arrays were built while every pivot was exactly 1.0 (its U
+ * sweeps never read the pivots), a handle whose creating matrix repeated a
+ * column in a row, and a distributed A return LSSP_AMD_EUNSUPPORTED with M
+ * unchanged and usable.
+ * Pattern rule, checked on the device with nothing of A trusted: A is n x n
+ * with M's n, every row's columns are strictly ascending and inside [0, n), and
+ * A's pattern is exactly that of the creating matrix after its column sort (a
+ * diagonal create had to insert stays absent).  At level >= 1 an entry of A on
+ * a fill position of the factor is therefore refused: a fresh create would
+ * build another symbolic pattern.  A violation, another n or a row range
+ * outside [0, nnz) returns LSSP_AMD_EINVAL, NULL arguments too, with everything
+ * a caller can read unchanged: nothing is written before the check has passed,
+ * and nothing can refuse after it (scalar ILU(0) replaces tiny pivots).
+ * The first call builds a plan kept until lssp_amd_ilu_destroy: the factor
+ * pattern with one flag byte per entry (matrix entry, fill, inserted
+ * diagonal), a factor value buffer, the reciprocal pivots, each row's diagonal
+ * position and the level lists -- 13 B per factor entry + 20 B per row of
+ * device memory; a handle that is never refactored allocates none of it (create
+ * keeps the flag bytes on the host, 1 B per factor entry).  A HIP error part-way
+ * returns LSSP_AMD_EHIP, after which M may only be destroyed. */
+int lssp_amd_iluk_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat *A);
 /* lssp_amd_ilu_create for a matrix that lives in HBM: the arguments have its
  * meaning, the matrix is the handle's device CSR.  No matrix array is copied to
  * the host, neither pattern nor values; a few words come back (row 0's entries,

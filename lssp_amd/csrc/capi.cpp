@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10500; }
+int lssp_amd_version(void) { return 10600; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -832,11 +832,13 @@ static int ilu_create(lssp_amd_ctx *c, int kind, int n, const int *Ap, const int
     if (kind == LSSP_AMD_ILUK && level < 0) level = 1;  // pc-iluk.cxx:583-592
     HostCSR L, U;
     int fst = LSSP_AMD_OK;
-    ilu_factor(c, kind, std::move(A), level, tol < 0 ? 1e-3 : tol, p, blk, L, U, &fst);
+    std::vector<unsigned char> fin;  // what lssp_amd_iluk_refactor needs of the pattern: 1 B per factor entry, host
+    ilu_factor(c, kind, std::move(A), level, tol < 0 ? 1e-3 : tol, p, blk, L, U, &fst, &fin);
     if (fst != LSSP_AMD_OK) return fst;
     lssp_amd_ilu *M = new lssp_amd_ilu();
     M->ctx = c;
     M->n = n;
+    M->fIn = std::move(fin);
     M->Lp = std::move(L.Ap);
     M->Lj = std::move(L.Aj);
     M->Lx = std::move(L.Ax);
@@ -860,13 +862,18 @@ static int ilu_create(lssp_amd_ctx *c, int kind, int n, const int *Ap, const int
 // the kept level lists) and both coefficient streams rewritten from it
 // (k_coef_refill); tiles, stream layout, hand-off buffers and claim counters
 // stay as ilu_create left them.
+static bool ilu0_tiled_handle(const lssp_amd_ilu *M)
+{
+    const LineILU &li = M->line;
+    return M->c_kind == LSSP_AMD_ILUK && M->c_level == 0 && (M->c_blk <= 0 || M->c_blk >= M->n) && M->bs == 0 &&
+           li.ntiles > 0 && li.kind == 0 && li.g2 == 0 && li.P * li.NJ <= 256;
+}
+
 int lssp_amd_ilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A)
 {
     if (!c || !M || !A) return LSSP_AMD_EINVAL;
     const LineILU &li = M->line;
-    const bool eligible = M->c_kind == LSSP_AMD_ILUK && M->c_level == 0 && (M->c_blk <= 0 || M->c_blk >= M->n) &&
-                          M->bs == 0 && li.ntiles > 0 && li.kind == 0 && li.g2 == 0 && li.P * li.NJ <= 256;
-    if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
+    if (!ilu0_tiled_handle(M) || A->dist) return LSSP_AMD_EUNSUPPORTED;
     if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
     const long fnnz = M->host_missing ? (long)M->dev_nnzL + M->dev_nnzU - M->n : (long)M->Lp[M->n] + M->Up[M->n] - M->n;
     if ((long)A->nnz != fnnz) return LSSP_AMD_EINVAL;
@@ -897,6 +904,74 @@ int lssp_amd_ilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *
             fprintf(stderr, "lssp_amd refactor: refill bytes %lld\n",
                     2 * (4LL * (M->n + 1) + 12LL * M->rf->nnz) +
                         8LL * (li.L.rows_total * li.L.NA + li.U.rows_total * li.U.NA));
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+    return LSSP_AMD_OK;
+}
+
+// Any one-block ILUK handle on the packet sweeps or the skewed ILU(1) line
+// sweeps: A's pattern matched against the kept flag bytes,
+// its values scattered onto the factor pattern (fill +0.0), k_ilu0_level over
+// the kept level lists, the sweeps' value arrays rewritten from the result.
+// Schedules, layouts, shadows, hand-off buffers and claim counters stay as
+// ilu_create left them.  A handle lssp_amd_ilu_refactor serves goes there.
+int lssp_amd_iluk_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A)
+{
+    if (!c || !M || !A) return LSSP_AMD_EINVAL;
+    if (ilu0_tiled_handle(M)) return lssp_amd_ilu_refactor(c, M, A);
+    const LineILU &li = M->line;
+    const bool packets = li.ntiles == 0 && M->lower.pk6_n > 0 && M->upper.pk6_n > 0;
+    const bool linef = li.ntiles > 0 && li.kind == 1 && li.g2 == 0;
+    // upper.unit: the single sweeps' arrays were built while every pivot was
+    // exactly 1.0, and the U sweeps then never read D
+    const bool eligible = M->c_kind == LSSP_AMD_ILUK && (M->c_blk <= 0 || M->c_blk >= M->n) && M->bs == 0 &&
+                          !M->fIn.empty() && !M->host_missing && !M->upper.unit && (packets || linef);
+    if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
+    if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    try {
+        LSSP_HIP(hipSetDevice(c->device));
+        double t0 = wall_time();
+        auto mark = [&](const char *phase) -> int {  // LSSP_AMD_SETUP_TIMES=1: the phases' own durations, the stream drained
+            if (!times) return LSSP_AMD_OK;
+            LSSP_HIP(hipStreamSynchronize(c->stream));
+            const double t = wall_time();
+            fprintf(stderr, "lssp_amd iluk_refactor: %-20s %10.6f s\n", phase, t - t0);
+            t0 = t;
+            return LSSP_AMD_OK;
+        };
+        LSSP_TRY(refactor_plan_build(c, M, true));
+        RefactorPlan &p = *M->rf;
+        if (!p.d_fin) return LSSP_AMD_EUNSUPPORTED;
+        LSSP_TRY(mark("plan"));
+        int ok = 0;
+        LSSP_TRY(iluk_match(c, p, M->n, A->nnz, A->Ap, A->Aj, &ok));
+        if (!ok) return LSSP_AMD_EINVAL;  // nothing written
+        LSSP_TRY(mark("match"));
+        LSSP_TRY(iluk_scatter(c, p, M->n, A->Ap, A->Ax));
+        LSSP_TRY(mark("scatter"));
+        LSSP_TRY(refactor_levels(c, p, M->n));
+        LSSP_TRY(mark("numeric"));
+        if (packets) {
+            LSSP_TRY(launch_pk6_refill_scalar(c, M->lower, false, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
+            LSSP_TRY(launch_pk6_refill_scalar(c, M->upper, true, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
+        } else {
+            LSSP_TRY(launch_linefill_refill(c, M->line, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
+        }
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        LSSP_TRY(mark("refill"));
+        // the device factors are ahead of Lx / Ux now, and of the sync-free arrays a
+        // single sweep built from those: the next reader refreshes the host
+        // copies, the next lssp_amd_ilu_trisolve rebuilds the arrays
+        std::lock_guard<std::mutex> lk(M->sync_free_mu);
+        M->host_stale = true;
+        for (TriSched *t : {&M->lower, &M->upper}) {
+            for (void *q : {(void *)t->perm, (void *)t->rp, (void *)t->cols, (void *)t->vals, (void *)t->diag})
+                if (q) (void)hipFree(q);
+            t->perm = t->rp = t->cols = nullptr;
+            t->vals = t->diag = nullptr;
+        }
     } catch (const std::exception &) {
         return LSSP_AMD_ENOMEM;
     }

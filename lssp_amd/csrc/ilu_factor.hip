@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "iluk_refactor_dev.h"
 #include "internal.h"
 
 namespace lssp_amd {
@@ -158,14 +159,16 @@ void refactor_plan_free(RefactorPlan *p)
 {
     if (!p) return;
     for (void *q : {(void *)p->d_Fp, (void *)p->d_Fj, (void *)p->d_Fx, (void *)p->d_dinv, (void *)p->d_rows,
-                    (void *)p->d_flag})
+                    (void *)p->d_flag, (void *)p->d_fin, (void *)p->d_dpos})
         if (q) (void)hipFree(q);
     delete p;
 }
 
 // F's row i = L's strict entries, the diagonal, U's strict entries (L keeps its
 // unit diagonal LAST, U its pivot FIRST): the pattern ilu_factor split them from
-int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M)
+// with_flags (lssp_amd_iluk_refactor's own routes): also the handle's flag bytes
+// and each row's diagonal position
+int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M, bool with_flags)
 {
     if (M->rf) return LSSP_AMD_OK;
     const int n = M->n;
@@ -184,6 +187,15 @@ int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M)
     p->nnz = nnz;
     std::vector<int> rows;
     level_lists(n, Fp, Fj, p->lev_off, rows);
+    std::vector<int> dpos;
+    if (with_flags) {
+        if ((long)M->fIn.size() != nnz) {
+            delete p;
+            return LSSP_AMD_EINVAL;
+        }
+        dpos.resize(n);
+        for (int i = 0; i < n; i++) dpos[i] = Fp[i] + (M->Lp[i + 1] - M->Lp[i] - 1);
+    }
     auto fill = [&]() -> int {
         LSSP_HIP(hipMalloc(&p->d_Fp, sizeof(int) * (n + 1)));
         LSSP_HIP(hipMalloc(&p->d_Fj, sizeof(int) * nnz));
@@ -194,6 +206,12 @@ int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M)
         LSSP_HIP(hipMemcpyAsync(p->d_Fp, Fp.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, c->stream));
         LSSP_HIP(hipMemcpyAsync(p->d_Fj, Fj.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, c->stream));
         LSSP_HIP(hipMemcpyAsync(p->d_rows, rows.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+        if (with_flags) {
+            LSSP_HIP(hipMalloc(&p->d_fin, (size_t)nnz));
+            LSSP_HIP(hipMalloc(&p->d_dpos, sizeof(int) * n));
+            LSSP_HIP(hipMemcpyAsync(p->d_fin, M->fIn.data(), (size_t)nnz, hipMemcpyHostToDevice, c->stream));
+            LSSP_HIP(hipMemcpyAsync(p->d_dpos, dpos.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+        }
         LSSP_HIP(hipStreamSynchronize(c->stream));
         return LSSP_AMD_OK;
     };
@@ -362,6 +380,57 @@ int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const i
 int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx)
 {
     LSSP_HIP(hipMemcpyAsync(p.d_Fx, dAx, sizeof(double) * p.nnz, hipMemcpyDeviceToDevice, c->stream));
+    return refactor_levels(c, p, n);
+}
+
+// ---------------------------------------------------------------------------
+// lssp_amd_iluk_refactor: the pattern rule and the scatter onto a pattern with
+// fill (iluk_refactor_dev.h), one row per lane, grid-strided
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_iluk_match(int n, int nnz, const int *__restrict__ Ap,
+                                                    const int *__restrict__ Aj, const int *__restrict__ Fp,
+                                                    const int *__restrict__ Fj, const unsigned char *__restrict__ fin,
+                                                    int *__restrict__ flag)
+{
+    int bad = 0;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256)
+        bad |= iluk_match_row((int)r, nnz, Ap, Aj, Fp, Fj, fin);
+    if (bad) atomicOr(flag, 1);
+}
+
+__global__ __launch_bounds__(256) void k_iluk_scatter(int n, const int *__restrict__ Ap, const double *__restrict__ Ax,
+                                                      const int *__restrict__ Fp,
+                                                      const unsigned char *__restrict__ fin, double *__restrict__ Fx)
+{
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256)
+        iluk_scatter_row((int)r, Ap, Ax, Fp, fin, Fx);
+}
+
+int iluk_match(lssp_amd_ctx *c, const RefactorPlan &p, int n, int nnz, const int *dAp, const int *dAj, int *ok)
+{
+    *ok = 0;
+    LSSP_HIP(hipMemsetAsync(p.d_flag, 0, sizeof(int), c->stream));
+    k_iluk_match<<<(unsigned)std::min<long>(((long)n + 255) / 256, 16384), 256, 0, c->stream>>>(n, nnz, dAp, dAj, p.d_Fp,
+                                                                                              p.d_Fj, p.d_fin, p.d_flag);
+    LSSP_HIP(hipGetLastError());
+    int bad = 1;
+    LSSP_HIP(hipMemcpyAsync(&bad, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    *ok = !bad;
+    return LSSP_AMD_OK;
+}
+
+int iluk_scatter(lssp_amd_ctx *c, RefactorPlan &p, int n, const int *dAp, const double *dAx)
+{
+    k_iluk_scatter<<<(unsigned)std::min<long>(((long)n + 255) / 256, 16384), 256, 0, c->stream>>>(n, dAp, dAx, p.d_Fp,
+                                                                                                p.d_fin, p.d_Fx);
+    LSSP_HIP(hipGetLastError());
+    return LSSP_AMD_OK;
+}
+
+// k_ilu0_level over the kept level lists on d_Fx, in place
+int refactor_levels(lssp_amd_ctx *c, RefactorPlan &p, int n)
+{
     const int nlev = (int)p.lev_off.size() - 1;
     for (int l = 0; l < nlev; l++) {
         const int cnt = p.lev_off[l + 1] - p.lev_off[l];

@@ -279,10 +279,12 @@ struct LineILU {
     double *d_g2L = nullptr, *d_g2U = nullptr;
 };
 
-// lssp_amd_ilu_refactor's state (ilu_factor.hip): the factor pattern F (row i =
-// L's strict part, the diagonal, U's strict part: the matrix's own pattern) and
-// the buffers k_ilu0_level works in, kept between refactors.  4 + 8 B per
-// entry, 4 + 8 + 4 B per row.
+// lssp_amd_ilu_refactor's and lssp_amd_iluk_refactor's state (ilu_factor.hip):
+// the factor pattern F (row i = L's strict part, the diagonal, U's strict part:
+// at level 0 the matrix's own pattern) and the buffers k_ilu0_level works in,
+// kept between refactors.  4 + 8 B per entry, 4 + 8 + 4 B per row; a plan of
+// lssp_amd_iluk_refactor's own routes adds the flag bytes and the diagonal
+// positions: 4 + 8 + 1 B per entry, 4 + 8 + 4 + 4 B per row.
 struct RefactorPlan {
     long nnz = 0;
     int *d_Fp = nullptr, *d_Fj = nullptr;
@@ -290,6 +292,9 @@ struct RefactorPlan {
     int *d_rows = nullptr;     // rows ordered by level of the strict-lower DAG
     std::vector<int> lev_off;  // host: d_rows[lev_off[l] .. lev_off[l + 1]) is level l
     int *d_flag = nullptr;     // the pattern compare's answer
+    // lssp_amd_iluk_refactor (nullptr in a plan lssp_amd_ilu_refactor built):
+    unsigned char *d_fin = nullptr;  // per entry of F: lssp_amd_ilu::fIn
+    int *d_dpos = nullptr;           // per row: the position of its diagonal in F
 };
 
 // lssp_amd_bilu_refactor's state (bilu_factor.hip), kept between refactors: the
@@ -350,6 +355,11 @@ struct lssp_amd_ilu {
     std::vector<int> bBp, bBj;
     std::vector<unsigned char> bIn;
     lssp_amd::BiluPlan *brf = nullptr;  // built by the first lssp_amd_bilu_refactor
+    // lssp_amd_ilu_create, ILUK with one block (lssp_amd_iluk_refactor's pattern
+    // rule): per entry of the factor pattern F, 1 = an entry of the sorted
+    // creating matrix, 0 = fill, 2 = an inserted diagonal (ilu_factor); empty:
+    // not such a handle, or the creating matrix repeated a column in a row
+    std::vector<unsigned char> fIn;
     // made by lssp_amd_ilu_create_dev: the host copies Lp .. Ux do not exist until
     // something reads them (refactor_host_factors splits them from the device F);
     // until then the entry counts are these
@@ -487,8 +497,12 @@ void sort_columns(HostCSR &A);
 // c != nullptr: ILUK's numeric ILU(0) runs on c's GPU (ilu_factor.hip), bitwise
 // the host restatement (LSSP_AMD_ILU_HOST=1 selects the host one); ILUT stays
 // on the host (pc-ilut.cxx:51-286 is sequential by row)
+// fin != nullptr, ILUK with one block: one byte per entry of the factor pattern
+// F (row i = L's strict part, the diagonal, U's strict part): 1 = an entry of the
+// sorted matrix, 0 = fill of level >= 1, 2 = a diagonal adjust_zero_diag
+// inserted; left empty otherwise, and when a row of A repeats a column
 void ilu_factor(lssp_amd_ctx *c, int kind, HostCSR &&A, int level, double tol, int p, int blk, HostCSR &L,
-                HostCSR &U, int *status);
+                HostCSR &U, int *status, std::vector<unsigned char> *fin = nullptr);
 int ilu0_factor_gpu(lssp_amd_ctx *c, int n, int blk, const std::vector<int> &Ap, const std::vector<int> &Aj,
                     std::vector<double> &Ax);
 // BILUK setup (ilu_setup.cpp, bilu_factor.hip): pc-biluk.cxx on the arithmetic of bilu_dev.h
@@ -571,11 +585,27 @@ void free_line_sweep(LineILU &li);
 // lssp_amd_ilu_refactor (capi.cpp).  ilu_factor.hip: the plan from the host
 // copies of the factor pattern; *same = A's device pattern equals it; the
 // numeric ILU(0) of Ax (device, plan order) into d_Fx; Lx / Ux from d_Fx.
-int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M);
+int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M, bool with_flags = false);
 void refactor_plan_free(RefactorPlan *p);
 int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same);
 int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx);
 int refactor_host_factors(lssp_amd_ilu *M);
+// lssp_amd_iluk_refactor's own routes (capi.cpp; ilu_factor.hip, DESIGN.md
+// 3.3c), on a plan built with the flag bytes.  iluk_match: *ok = A's device
+// pattern obeys the pattern rule (nothing written).  iluk_scatter_numeric: A's
+// values onto F (fill +0.0, inserted diagonals ZERO_DIAG_TOL), then
+// refactor_numeric's launches.
+int iluk_match(lssp_amd_ctx *c, const RefactorPlan &p, int n, int nnz, const int *dAp, const int *dAj, int *ok);
+int iluk_scatter(lssp_amd_ctx *c, RefactorPlan &p, int n, const int *dAp, const double *dAx);
+int refactor_levels(lssp_amd_ctx *c, RefactorPlan &p, int n);
+// trisolve.hip: launch_pk6_refill for a scalar factor F (dpos: each row's
+// diagonal position); the U sweep's records also get D = the stored pivot
+int launch_pk6_refill_scalar(lssp_amd_ctx *c, const TriSched &t, bool upper, int n, const int *Fp, const int *Fj,
+                             const int *dpos, const double *Fx);
+// linefill.hip: both coefficient streams of a k_linef factor rewritten from
+// the factored values Fx on the pattern (Fp, Fj); every slot is written
+int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const int *dpos,
+                           const double *Fx);
 // lssp_amd_ilu_create_dev (ilu_factor.hip), for a device CSR (n rows, nnz
 // entries) and a box nx x ny x nz = n.  box_pattern_check: *ok = the pattern is
 // exactly the complete natural-order 5-/7-point stencil of that box, rows

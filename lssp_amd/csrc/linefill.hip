@@ -60,6 +60,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "iluk_refactor_dev.h"
 #include "internal.h"
 #include "linesweep_dev.h"
 
@@ -1209,6 +1210,59 @@ int launch_linefill_apply_tail(lssp_amd_ctx *c, const LineILU &li, double *x, co
     LSSP_TRY(linef_sweep(c, li, 0, li.d_lstream, li.d_ustream, 2));
     LSSP_TRY(linef_sweep(c, li, 1, li.d_ustream, x, 1, &T));
     *tail_waves = (long)std::min(li.U.ntiles, c->num_cus);  // (the tail's claimants: workgroups)
+    return LSSP_AMD_OK;
+}
+
+// lssp_amd_iluk_refactor: FillCoef::build + fill_upload on the device.  Workgroup
+// (x, tile): 256 consecutive slots of the tile's T * P * nj, one per lane.  A
+// lane finds its slot's sweep row (linef_slot_row), gathers that row's NA
+// coefficients from the factored values (linef_coef_row; +0.0 for a slot off
+// the grid and for a missing neighbour) into LDS, and the workgroup then stores
+// the 256 * NA doubles in stream order, consecutive lanes to consecutive
+// addresses.  Every slot of every tile is written, skipped tiles included.
+__global__ __launch_bounds__(256) void k_linef_refill(const LineTile *__restrict__ tiles, int ntiles, int NA, int upper,
+                                                      int nx, int ny, long n, const int *__restrict__ Fp,
+                                                      const int *__restrict__ Fj, const int *__restrict__ dpos,
+                                                      const double *__restrict__ Fx, double *__restrict__ coef)
+{
+    __shared__ double sm[256 * 7];
+    const long pl = (long)nx * ny;
+    for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
+        const LineTile d = tiles[t];
+        const long slots = (long)d.T * lf::P * d.nj;
+        for (long s0 = blockIdx.x * 256L; s0 < slots; s0 += (long)gridDim.x * 256) {
+            const long s = s0 + threadIdx.x;
+            double *mine = sm + threadIdx.x * NA;
+            if (s < slots) {
+                const long rs = linef_slot_row(s, d.j0, d.nj, d.k0, d.np, nx, ny);
+                if (rs >= 0 && rs < n) linef_coef_row(rs, upper != 0, n, nx, pl, NA, Fp, Fj, dpos, Fx, mine);
+                else
+                    for (int a = 0; a < NA; a++) mine[a] = 0.0;
+            }
+            __syncthreads();
+            const long cnt = (slots - s0 < 256 ? slots - s0 : 256) * NA;
+            double *dst = coef + (d.cbase + s0) * NA;
+            for (long e = threadIdx.x; e < cnt; e += 256) dst[e] = sm[e];
+            __syncthreads();
+        }
+    }
+}
+
+int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const int *dpos,
+                           const double *Fx)
+{
+    if (li.kind != 1 || li.g2 || li.ntiles <= 0) return LSSP_AMD_EUNSUPPORTED;
+    static_assert(lf::P == LINEF_P, "iluk_refactor_dev.h restates the tile's planes");
+    for (int which = 0; which < 2; which++) {
+        const LineSweep &ls = which ? li.U : li.L;
+        if ((long)ls.nx * ls.ny * ls.nz != n || (ls.NA != 6 && ls.NA != 7)) return LSSP_AMD_EINVAL;
+        const long maxslots = (long)ls.tmax * lf::P * lf::NJ;
+        const dim3 grid((unsigned)std::min<long>((maxslots + 255) / 256, 1024), (unsigned)std::min(ls.ntiles, 65535));
+        k_linef_refill<<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.ntiles, ls.NA, which, ls.nx, ls.ny, n, Fp, Fj, dpos,
+                                                    Fx, ls.d_coef);
+        LSSP_HIP(hipGetLastError());
+    }
+    li.lstream_of = nullptr;
     return LSSP_AMD_OK;
 }
 

@@ -409,6 +409,14 @@ class DILU:
         handle stays as it was in every such case."""
         _ck(self.dev.L.lssp_amd_bilu_refactor(self.dev.h, self.h, A.h), "bilu_refactor")
 
+    def iluk_refactor(self, A: DMat):
+        """Factor any one-block ILUK handle again from the values A holds now, keeping every
+        schedule (lssp_amd_iluk_refactor): what refactor() serves, plus handles on the packet
+        sweeps and on the skewed ILU(1) line sweeps, at any level.  A must have the creating
+        matrix's (column-sorted) pattern exactly (status 1 otherwise); any other handle raises
+        LsspError with status 6 (unsupported).  The handle stays as it was in every such case."""
+        _ck(self.dev.L.lssp_amd_iluk_refactor(self.dev.h, self.h, A.h), "iluk_refactor")
+
     def apply(self, x: DVec, rhs: DVec):
         """x = U^-1 L^-1 rhs (lssp_pc_ilu_solve, solver-tri.cxx:57-60)"""
         _ck(self.dev.L.lssp_amd_ilu_apply(self.dev.h, self.h, x.ptr, rhs.ptr), "ilu_apply")
