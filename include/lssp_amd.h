@@ -364,11 +364,13 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      lssp_amd_solve runs without a host copy of the matrix.
  *      The tiled line-sweep ILU(0) of a natural-order 5-/7-point box is made
  *      from the matrix handle without a host copy either
- *      (lssp_amd_ilu_create_dev, below).
+ *      (lssp_amd_ilu_create_dev, below), and so is the ILU(1) of such a box on
+ *      the skewed line sweeps, the reference's default level
+ *      (lssp_amd_iluk_create_dev).
  *      What still goes through the host: every other ILU setup
  *      (lssp_amd_ilu_create / lssp_amd_bilu_create take host arrays, as the
  *      reference factors on the host; download the CSR for them: ILUT, level
- *      >= 1, block-Jacobi, BILUK, general and small 2-D factors), and the
+ *      >= 2, block-Jacobi, BILUK, general and small 2-D factors), and the
  *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
  *      only when the PATTERN is new: new values on the same pattern stay on the
  *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor /
@@ -498,7 +500,8 @@ int lssp_amd_bilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_ma
  * lssp_amd_ilu_apply_async; the call returns when the stream has finished.
  * A superset of lssp_amd_ilu_refactor: a handle eligible there (one made by
  * lssp_amd_ilu_create_dev included) takes that path unchanged, so one call
- * serves every ILUK handle.  Newly eligible: M from lssp_amd_ilu_create with
+ * serves every ILUK handle.  A level-1 handle lssp_amd_iluk_create_dev made is
+ * eligible from birth (it carries its plan).  Newly eligible: M from lssp_amd_ilu_create with
  * kind ILUK, any level (negative: the default 1), one block (blk <= 0 or >= n),
  * whose sweeps run either on packet schedules (lssp_amd_ilu_sweep_layout: *line
  * == 0; general patterns, ILU(k >= 2) of stencils, boxes with holes) or on the
@@ -548,11 +551,44 @@ int lssp_amd_iluk_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_ma
  * Jacobi, an unsorted row, a missing diagonal or neighbour, a matrix that is
  * no such box, a small 2-D grid on the one-workgroup sweeps
  * (lssp_amd_ilu_sweep_layout *lines == ny there), LSSP_AMD_LINE=0, a distributed
- * A; use lssp_amd_ilu_create for those.  NULL arguments, a kind that is neither
- * ILUK nor ILUT, or nrows != ncols: LSSP_AMD_EINVAL.  A HIP error part-way:
- * LSSP_AMD_EHIP, everything freed.  Returns when the stream has finished. */
+ * A; use lssp_amd_ilu_create for those -- or lssp_amd_iluk_create_dev (below),
+ * which also makes the level-1 handle on the device.  NULL arguments, a kind
+ * that is neither ILUK nor ILUT, or nrows != ncols: LSSP_AMD_EINVAL.  A HIP
+ * error part-way: LSSP_AMD_EHIP, everything freed.  Returns when the stream has
+ * finished. */
 int lssp_amd_ilu_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p,
                             int blk, lssp_amd_ilu **out);
+/* The same for every device-made ILUK handle, the reference's default level
+ * included (a superset of lssp_amd_ilu_create_dev, as lssp_amd_iluk_refactor is
+ * of lssp_amd_ilu_refactor; the arguments are the same).  Whatever
+ * lssp_amd_ilu_create_dev accepts goes to it unchanged.  Newly eligible: kind
+ * ILUK, level 1 or level < 0 (the default, 1), one block (blk <= 0 or >= n), A
+ * single-rank and square with exactly the pattern of a complete natural-order
+ * box -- column-sorted rows that hold their diagonal and every grid neighbour
+ * that exists; a 7-point box with nx >= 3, ny >= 3, nz >= 2 or a 5-point grid
+ * with nx >= 3, ny >= 3 -- whose ILU(1) lssp_amd_ilu_create would run on the
+ * skewed line sweeps (lssp_amd_ilu_sweep_layout: 2, 16, 8).  The factor
+ * pattern, its fill flags, the level lists (row (i, j, k) is on level i + 2 j +
+ * 3 k) and the sweeps' tiles then follow from the grid alone; the values go
+ * through lssp_amd_iluk_refactor's own kernels.  No matrix array is copied to
+ * the host (row 0's entries and flag words come back).  The handle is bitwise
+ * lssp_amd_ilu_create(ILUK, level 1)'s of the same matrix in lssp_amd_ilu_apply
+ * / _apply_async + _check / _trisolve / lssp_amd_solve, lssp_amd_ilu_info,
+ * _sweep_layout and _get_factors (the host copies of the factors are made on
+ * the first call that reads them); it owns what it needs, so A may be
+ * destroyed, and it is made with its refactor plan, flag bytes included (13 B
+ * per factor entry + 20 B per row): lssp_amd_iluk_refactor is eligible on it at
+ * once and builds nothing.
+ * LSSP_AMD_EUNSUPPORTED with *out == NULL, nothing allocated, A and ctx
+ * untouched: ILUT, level >= 2, block-Jacobi, nx == 2 (or ny == 2), a small 2-D
+ * grid on the one-workgroup sweeps (*lines == ny; LSSP_AMD_LINEG=0 keeps the
+ * tiles), LSSP_AMD_LINE=0, a distributed A, an unsorted row, a missing diagonal
+ * or neighbour, any matrix that is no such box; use lssp_amd_ilu_create for
+ * those.  NULL arguments, a kind that is neither ILUK nor ILUT, or nrows !=
+ * ncols: LSSP_AMD_EINVAL.  A HIP error part-way: LSSP_AMD_EHIP, everything
+ * freed.  Returns when the stream has finished. */
+int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p,
+                             int blk, lssp_amd_ilu **out);
 
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);

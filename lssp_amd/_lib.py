@@ -112,6 +112,7 @@ SIGNATURES = {
     "lssp_amd_bilu_refactor": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_iluk_refactor": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_ilu_create_dev": (_ci, [_vp, _vp, _ci, _ci, _cd, _ci, _ci, _pvp]),
+    "lssp_amd_iluk_create_dev": (_ci, [_vp, _vp, _ci, _ci, _cd, _ci, _ci, _pvp]),
     "lssp_amd_poisson_nnz": (_cl, [_ci, _ci]),
     "lssp_amd_poisson_rows": (_ci, [_ci, _ci, _cl, _cl, _vp, _vp, _vp]),
 }

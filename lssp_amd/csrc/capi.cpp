@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10600; }
+int lssp_amd_version(void) { return 10700; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -923,10 +923,13 @@ int lssp_amd_iluk_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat 
     const LineILU &li = M->line;
     const bool packets = li.ntiles == 0 && M->lower.pk6_n > 0 && M->upper.pk6_n > 0;
     const bool linef = li.ntiles > 0 && li.kind == 1 && li.g2 == 0;
+    // a handle lssp_amd_iluk_create_dev made is born with its plan, flag bytes
+    // included: it needs neither the host flags nor the host factor copies
+    const bool planned = M->rf && M->rf->d_fin;
     // upper.unit: the single sweeps' arrays were built while every pivot was
     // exactly 1.0, and the U sweeps then never read D
     const bool eligible = M->c_kind == LSSP_AMD_ILUK && (M->c_blk <= 0 || M->c_blk >= M->n) && M->bs == 0 &&
-                          !M->fIn.empty() && !M->host_missing && !M->upper.unit && (packets || linef);
+                          (planned || (!M->fIn.empty() && !M->host_missing)) && !M->upper.unit && (packets || linef);
     if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
     if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
     static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
@@ -978,6 +981,33 @@ int lssp_amd_iluk_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat 
     return LSSP_AMD_OK;
 }
 
+// The box a device matrix claims to be, from row 0's few words and the entry
+// count (both device creates): row 0 of a complete natural-order box holds {0,
+// 1, nx, nx * ny} (2-D: {0, 1, nx}); strict = the stencil's entries on each side
+// of the diagonal.  EUNSUPPORTED when no box has that row 0 and that count; the
+// pattern itself is box_pattern_check's to judge.
+static int box_geometry_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, long &nx, long &ny, long &nz, long &strict)
+{
+    const int n = A->nrows, nnz = A->nnz;
+    if (nnz < 3) return LSSP_AMD_EUNSUPPORTED;
+    int h_p[2] = {0, 0}, h_j[4] = {0, 0, 0, 0};
+    LSSP_HIP(hipMemcpyAsync(h_p, A->Ap, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h_j, A->Aj, sizeof(int) * std::min(nnz, 4), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    const int len0 = h_p[1] - h_p[0];
+    if (h_p[0] != 0 || (len0 != 3 && len0 != 4) || len0 > nnz || h_j[0] != 0 || h_j[1] != 1)
+        return LSSP_AMD_EUNSUPPORTED;
+    nx = h_j[2];
+    const long plane = len0 == 4 ? (long)h_j[3] : (long)n;
+    if (nx < 2 || plane < nx || plane % nx || n % plane) return LSSP_AMD_EUNSUPPORTED;
+    ny = plane / nx;
+    nz = n / plane;
+    if ((len0 == 4) != (nz > 1)) return LSSP_AMD_EUNSUPPORTED;
+    strict = (nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1);
+    if (2 * strict + n != (long)nnz) return LSSP_AMD_EUNSUPPORTED;
+    return LSSP_AMD_OK;
+}
+
 // lssp_amd_ilu_create for a box matrix in HBM: what ilu_create builds on the
 // host from the factors is built here from the grid (tiles, layouts, buffers:
 // build_line_sweep_box) and on the device from the matrix (pattern check, level
@@ -1000,21 +1030,8 @@ static int ilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int 
         t0 = t;
         return LSSP_AMD_OK;
     };
-    // geometry: row 0 of a box holds {0, 1, nx, nx * ny} (2-D: {0, 1, nx})
-    if (nnz < 3) return LSSP_AMD_EUNSUPPORTED;
-    int h_p[2] = {0, 0}, h_j[4] = {0, 0, 0, 0};
-    LSSP_HIP(hipMemcpyAsync(h_p, A->Ap, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    LSSP_HIP(hipMemcpyAsync(h_j, A->Aj, sizeof(int) * std::min(nnz, 4), hipMemcpyDeviceToHost, c->stream));
-    LSSP_HIP(hipStreamSynchronize(c->stream));
-    const int len0 = h_p[1] - h_p[0];
-    if (h_p[0] != 0 || (len0 != 3 && len0 != 4) || len0 > nnz || h_j[0] != 0 || h_j[1] != 1)
-        return LSSP_AMD_EUNSUPPORTED;
-    const long nx = h_j[2], plane = len0 == 4 ? (long)h_j[3] : (long)n;
-    if (nx < 2 || plane < nx || plane % nx || n % plane) return LSSP_AMD_EUNSUPPORTED;
-    const long ny = plane / nx, nz = n / plane;
-    if ((len0 == 4) != (nz > 1)) return LSSP_AMD_EUNSUPPORTED;
-    const long strict = (nx - 1) * ny * nz + nx * (ny - 1) * nz + nx * ny * (nz - 1);  // on each side of the diagonal
-    if (2 * strict + n != (long)nnz) return LSSP_AMD_EUNSUPPORTED;
+    long nx, ny, nz, strict;
+    LSSP_TRY(box_geometry_dev(c, A, nx, ny, nz, strict));
     if (!line_box_tiled((int)nx, (int)ny, (int)nz)) return LSSP_AMD_EUNSUPPORTED;
     int ok = 0;
     LSSP_TRY(box_pattern_check(c, n, nnz, A->Ap, A->Aj, (int)nx, (int)ny, (int)nz, &ok));
@@ -1071,6 +1088,99 @@ int lssp_amd_ilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, in
         return LSSP_AMD_EINVAL;
     try {
         return ilu_create_dev(c, A, kind, level, blk, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+// The same for the reference's default level: the ILU(1) of a complete box on
+// the skewed k_linef sweeps.  The pattern-dependent pieces
+// follow from the grid (F, its flags, diagonal positions and level lists in
+// closed form: iluk_create_dev.h; tiles, layouts and buffers:
+// build_linefill_box); the value-dependent ones are lssp_amd_iluk_refactor's
+// (iluk_scatter, k_ilu0_level, k_linef_refill).
+static int iluk1_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int blk, lssp_amd_ilu **out)
+{
+    const int n = A->nrows, nnz = A->nnz;
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    LSSP_HIP(hipSetDevice(c->device));
+    const double t_start = wall_time();
+    double t0 = t_start;
+    auto mark = [&](const char *phase) -> int {  // LSSP_AMD_SETUP_TIMES=1: the phases' own durations, the stream drained
+        if (!times) return LSSP_AMD_OK;
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        const double t = wall_time();
+        fprintf(stderr, "lssp_amd iluk_create_dev: %-14s %10.6f s\n", phase, t - t0);
+        t0 = t;
+        return LSSP_AMD_OK;
+    };
+    long nx, ny, nz, strict;
+    LSSP_TRY(box_geometry_dev(c, A, nx, ny, nz, strict));
+    if (!linefill_box_tiled((int)nx, (int)ny, (int)nz)) return LSSP_AMD_EUNSUPPORTED;
+    const long fnnz = fill1_nnz((int)nx, (int)ny, (int)nz);
+    if (fnnz > 0x7fffffffL) return LSSP_AMD_EUNSUPPORTED;
+    int ok = 0;
+    LSSP_TRY(box_pattern_check(c, n, nnz, A->Ap, A->Aj, (int)nx, (int)ny, (int)nz, &ok));
+    if (!ok) return LSSP_AMD_EUNSUPPORTED;
+    LSSP_TRY(mark("pattern check"));
+
+    lssp_amd_ilu *M = new lssp_amd_ilu();
+    M->ctx = c;
+    M->n = n;
+    M->c_kind = kind;
+    M->c_level = 1;
+    M->c_blk = blk;
+    auto build = [&]() -> int {
+        LSSP_TRY(fill1_plan_pattern(c, n, (int)nx, (int)ny, (int)nz, &M->rf));
+        LSSP_TRY(mark("F pattern"));
+        LSSP_TRY(fill1_plan_levels(c, *M->rf, n, (int)nx, (int)ny, (int)nz));
+        LSSP_TRY(mark("levels"));
+        LSSP_TRY(iluk_scatter(c, *M->rf, n, A->Ap, A->Ax));
+        LSSP_TRY(mark("scatter"));
+        LSSP_TRY(refactor_levels(c, *M->rf, n));
+        LSSP_TRY(mark("numeric"));
+        LSSP_TRY(build_linefill_box(c, (int)nx, (int)ny, (int)nz, M->line));
+        LSSP_TRY(mark("allocation"));
+        LSSP_TRY(launch_linefill_refill(c, M->line, n, M->rf->d_Fp, M->rf->d_Fj, M->rf->d_dpos, M->rf->d_Fx));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        LSSP_TRY(mark("refill"));
+        return LSSP_AMD_OK;
+    };
+    int st;
+    try {
+        st = build();
+    } catch (const std::exception &) {
+        st = LSSP_AMD_ENOMEM;
+    }
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);  // nothing of the handle is in flight when it is freed
+        lssp_amd_ilu_destroy(M);
+        return st;
+    }
+    // what ilu_upload's level passes report: row (i, j, k) is on level i + 2 j + 3 k
+    // of L's DAG and on the mirrored level of U's
+    M->lower.n = M->upper.n = n;
+    M->lower.nlevels = M->upper.nlevels = (int)(nx + 2 * ny + 3 * nz - 5);
+    M->host_missing = M->host_stale = true;
+    M->dev_nnzL = M->dev_nnzU = (int)((fnnz + n) / 2);
+    M->setup_seconds = wall_time() - t_start;
+    *out = M;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_iluk_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int level, double tol, int p, int blk,
+                             lssp_amd_ilu **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !A || !out || A->nrows <= 0 || A->nrows != A->ncols || (kind != LSSP_AMD_ILUK && kind != LSSP_AMD_ILUT))
+        return LSSP_AMD_EINVAL;
+    // level 0 (and everything lssp_amd_ilu_create_dev refuses for other reasons than the level)
+    if (kind != LSSP_AMD_ILUK || level == 0) return lssp_amd_ilu_create_dev(c, A, kind, level, tol, p, blk, out);
+    if (level < 0) level = 1;  // the default (pc-iluk.cxx:583-592)
+    if (level != 1 || !(blk <= 0 || blk >= A->nrows) || A->dist || A->nhalo > 0) return LSSP_AMD_EUNSUPPORTED;
+    try {
+        return iluk1_create_dev(c, A, kind, blk, out);
     } catch (const std::exception &) {
         return LSSP_AMD_ENOMEM;
     }

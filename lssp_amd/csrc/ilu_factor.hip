@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "iluk_create_dev.h"
 #include "iluk_refactor_dev.h"
 #include "internal.h"
 
@@ -360,6 +361,117 @@ int refactor_plan_from_box(lssp_amd_ctx *c, int n, int nnz, const int *dAp, cons
     }
     *out = p;
     return LSSP_AMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// lssp_amd_iluk_create_dev: the plan of a complete box's ILU(1) in closed form
+// (iluk_create_dev.h), one row per lane, grid-strided
+// ---------------------------------------------------------------------------
+// Fp (row n - 1 also writes Fp[n]), Fj, the flag bytes and the diagonal
+// positions.  A row whose range would leave [0, fnnz) (never, on a box) is
+// dropped and ORs *flag, as does an end of the last row other than fnnz.
+__global__ __launch_bounds__(256) void k_fill1_pattern(int n, long fnnz, int nx, int ny, int nz, int *__restrict__ Fp,
+                                                       int *__restrict__ Fj, unsigned char *__restrict__ fin,
+                                                       int *__restrict__ dpos, int *__restrict__ flag)
+{
+    bool bad = false;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256) {
+        const int i = (int)(r % nx);
+        const long q = r / nx;
+        const int j = (int)(q % ny), k = (int)(q / ny);
+        const long s = fill1_row_start(i, j, k, nx, ny, nz);
+        const int len = fill1_row_len(i, j, k, nx, ny, nz);
+        if (s < 0 || s + len > fnnz) {
+            bad = true;
+            continue;
+        }
+        int dp = 0;
+        fill1_row(i, j, k, nx, ny, nz, Fj + s, fin + s, &dp);
+        Fp[r] = (int)s;
+        dpos[r] = (int)s + dp;
+        if (r == n - 1) {
+            Fp[n] = (int)(s + len);
+            bad |= s + len != fnnz;
+        }
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// d_rows: tab = S3[0 .. nlev), then lev_off[0 .. nlev].  A position outside
+// [0, n) (never, on a box) is dropped and ORs *flag.
+__global__ __launch_bounds__(256) void k_fill1_levels(int n, int nx, int ny, int nlev, const int *__restrict__ tab,
+                                                      int *__restrict__ rows, int *__restrict__ flag)
+{
+    bool bad = false;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256) {
+        const int i = (int)(r % nx);
+        const long q = r / nx;
+        const int j = (int)(q % ny), k = (int)(q / ny);
+        const long pos = fill1_level_pos(i, j, k, nx, tab, tab + nlev);
+        if (pos < 0 || pos >= n) bad = true;
+        else rows[pos] = (int)r;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+long fill1_nnz(int nx, int ny, int nz) { return fill1_row_start(0, 0, nz, nx, ny, nz); }
+
+int fill1_plan_pattern(lssp_amd_ctx *c, int n, int nx, int ny, int nz, RefactorPlan **out)
+{
+    *out = nullptr;
+    const long fnnz = fill1_nnz(nx, ny, nz);
+    if (nx < 1 || ny < 1 || nz < 1 || (long)nx * ny * nz != (long)n || fnnz > 0x7fffffffL) return LSSP_AMD_EINVAL;
+    RefactorPlan *p = new RefactorPlan();
+    p->nnz = fnnz;
+    auto fill = [&]() -> int {
+        LSSP_HIP(hipMalloc(&p->d_Fp, sizeof(int) * ((size_t)n + 1)));
+        LSSP_HIP(hipMalloc(&p->d_Fj, sizeof(int) * (size_t)fnnz));
+        LSSP_HIP(hipMalloc(&p->d_Fx, sizeof(double) * (size_t)fnnz));
+        LSSP_HIP(hipMalloc(&p->d_dinv, sizeof(double) * (size_t)n));
+        LSSP_HIP(hipMalloc(&p->d_rows, sizeof(int) * (size_t)n));
+        LSSP_HIP(hipMalloc(&p->d_flag, sizeof(int)));
+        LSSP_HIP(hipMalloc(&p->d_fin, (size_t)fnnz));
+        LSSP_HIP(hipMalloc(&p->d_dpos, sizeof(int) * (size_t)n));
+        LSSP_HIP(hipMemsetAsync(p->d_flag, 0, sizeof(int), c->stream));
+        k_fill1_pattern<<<(unsigned)std::min<long>(((long)n + 255) / 256, 16384), 256, 0, c->stream>>>(
+            n, fnnz, nx, ny, nz, p->d_Fp, p->d_Fj, p->d_fin, p->d_dpos, p->d_flag);
+        LSSP_HIP(hipGetLastError());
+        return LSSP_AMD_OK;
+    };
+    const int st = fill();
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);
+        refactor_plan_free(p);
+        return st;
+    }
+    *out = p;
+    return LSSP_AMD_OK;
+}
+
+int fill1_plan_levels(lssp_amd_ctx *c, RefactorPlan &p, int n, int nx, int ny, int nz)
+{
+    if (nx < 1 || ny < 1 || nz < 1) return LSSP_AMD_EINVAL;
+    const int nlev = fill1_nlev(nx, ny, nz);
+    std::vector<int> tab(2 * (size_t)nlev + 1);  // the two tables from the grid alone (no pass over the matrix)
+    if (fill1_level_tables(nx, ny, nz, tab.data()) != (long)n) return LSSP_AMD_EINVAL;
+    p.lev_off.assign(tab.begin() + nlev, tab.end());
+    int *d_tab = nullptr;
+    auto fill = [&]() -> int {
+        LSSP_HIP(hipMalloc(&d_tab, sizeof(int) * tab.size()));
+        LSSP_HIP(hipMemcpyAsync(d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+        k_fill1_levels<<<(unsigned)std::min<long>(((long)n + 255) / 256, 16384), 256, 0, c->stream>>>(n, nx, ny, nlev, d_tab,
+                                                                                                    p.d_rows, p.d_flag);
+        LSSP_HIP(hipGetLastError());
+        int bad = 1;
+        LSSP_HIP(hipMemcpyAsync(&bad, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        return bad ? LSSP_AMD_EINVAL : LSSP_AMD_OK;
+    };
+    const int st = fill();
+    if (st != LSSP_AMD_OK) (void)hipStreamSynchronize(c->stream);
+    if (d_tab) (void)hipFree(d_tab);
+    return st;
 }
 
 int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same)

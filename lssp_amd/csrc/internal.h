@@ -360,7 +360,7 @@ struct lssp_amd_ilu {
     // creating matrix, 0 = fill, 2 = an inserted diagonal (ilu_factor); empty:
     // not such a handle, or the creating matrix repeated a column in a row
     std::vector<unsigned char> fIn;
-    // made by lssp_amd_ilu_create_dev: the host copies Lp .. Ux do not exist until
+    // made by lssp_amd_ilu_create_dev / lssp_amd_iluk_create_dev: the host copies Lp .. Ux do not exist until
     // something reads them (refactor_host_factors splits them from the device F);
     // until then the entry counts are these
     bool host_missing = false;
@@ -563,6 +563,15 @@ int build_line_sweep_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li);
 int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
                    const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
                    const std::vector<double> &Ux, LineILU &li);
+// lssp_amd_iluk_create_dev: the skewed k_linef sweeps of the ILU(1) of a
+// complete nx x ny x nz box from the grid alone -- build_linefill's tiles,
+// layouts and buffers, the coefficient streams zeroed for
+// launch_linefill_refill.  linefill_box_tiled: build_linefill would put that
+// factor on the skewed 16 x 8 tiles (line_enabled, detect_fill1's sizes, not
+// the one-workgroup route); else EUNSUPPORTED.
+bool line_enabled();  // linesweep.hip: LSSP_AMD_LINE=0 turns every line sweep off
+bool linefill_box_tiled(int nx, int ny, int nz);
+int build_linefill_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li);
 int launch_linefill_apply(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs);
 struct LineTail;
 // small 2-D grids on one workgroup (linefill.hip): cl / cu hold the L / U rows in
@@ -617,6 +626,16 @@ int box_pattern_check(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int
                       int *ok);
 int refactor_plan_from_box(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int nx, int ny, int nz,
                            RefactorPlan **out);
+// lssp_amd_iluk_create_dev (ilu_factor.hip, iluk_create_dev.h):
+// the plan of the ILU(1) of such a box, flag bytes and diagonal positions
+// included, in closed form.  fill1_nnz: F's entry count (each of L and U holds
+// (that + n) / 2).  fill1_plan_pattern: the buffers, and F's pattern written by
+// one pass (no wait).  fill1_plan_levels: row (i, j, k) has level i + 2 j + 3 k;
+// the level lists from two small host tables, then both passes' flag word read
+// back: EINVAL when a position fell outside its array.
+long fill1_nnz(int nx, int ny, int nz);
+int fill1_plan_pattern(lssp_amd_ctx *c, int n, int nx, int ny, int nz, RefactorPlan **out);
+int fill1_plan_levels(lssp_amd_ctx *c, RefactorPlan &p, int n, int nx, int ny, int nz);
 // linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
 // the factored values Fx on the pattern (Fp, Fj); every slot is written
 int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);

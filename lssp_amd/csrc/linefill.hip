@@ -105,6 +105,26 @@ __host__ __device__ inline long g2_at(long v, int NW, int NC, int k, int j)  // 
 // ---------------------------------------------------------------------------
 namespace {
 
+// the grids whose ILU(1) pattern the sweeps take: six (2-D: three) distinct
+// offsets need nx, ny >= 3
+bool fill1_sizes(long nx, long ny, long nz) { return nx >= 3 && ny >= 3 && nz >= 1; }
+// a small 2-D grid runs on one workgroup (k_lineg) unless LSSP_AMD_LINEG=0 keeps the tiles
+bool fill1_lineg_route(const LineGeom &g)
+{
+    const char *e = getenv("LSSP_AMD_LINEG");  // (read per build: tests select either path)
+    return g.nz == 1 && g.ny <= G2_MAXNY && lineg_fits(g, 1) && !(e && !atoi(e));
+}
+// a complete box's geometry as detect_fill1 reports it for an ILUK factor
+void fill1_box_geom(int nx, int ny, int nz, LineGeom &g)
+{
+    g.nx = nx;
+    g.ny = ny;
+    g.nz = nz;
+    g.kin.assign(nz, 1);
+    g.kin[0] = 0;
+    g.unitL = true;  // ILUK's L diagonal is 1.0
+}
+
 // L / U rows exactly the 7-point ILU(1) pattern of an nx x ny x nz grid, or
 // the 5-point one of an nx x ny grid (nz = 1); nx, ny >= 3, no block-Jacobi cuts
 bool detect_fill1(int n, const std::vector<int> &Lp, const std::vector<int> &Lj, const std::vector<double> &Lx,
@@ -132,11 +152,11 @@ bool detect_fill1(int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
     const long nx = offs[2], pl = no == 6 ? offs[5] : n;
     if (offs[0] != 1 || offs[1] != nx - 1) return false;
     if (no == 6 && (offs[3] != pl - nx || offs[4] != pl - 1)) return false;
-    if (nx < 3 || pl % nx || n % pl) return false;
+    if (nx < 1 || pl % nx || n % pl) return false;
     g.nx = (int)nx;
     g.ny = (int)(pl / nx);
     g.nz = (int)(n / pl);
-    if (g.ny < 3 || (no == 6) != (g.nz >= 2)) return false;
+    if (!fill1_sizes(g.nx, g.ny, g.nz) || (no == 6) != (g.nz >= 2)) return false;
     std::atomic<bool> ok{true}, unit{true};
     parallel_for(n, [&](long r0, long r1) {
         for (long r = r0; r < r1 && ok.load(std::memory_order_relaxed); r++) {
@@ -219,11 +239,13 @@ int fill_T(int nx, int nj, int np)
     return (T + lf::LV - 1) / lf::LV * lf::LV;
 }
 
-int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, int W, const FillCoef &src,
-                LineSweep &ls)
+// src == nullptr: the coefficient stream is zeroed on the context's stream
+// (launch_linefill_refill writes it)
+int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, int W, const FillCoef *src,
+                int NA, LineSweep &ls)
 {
     using namespace lf;
-    const int nx = g.nx, NA = src.NA;
+    const int nx = g.nx;
     std::vector<LineTile> tt = tiles;
     long rows_total = 0;
     int tmax = 0;
@@ -234,8 +256,10 @@ int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> 
         tmax = std::max(tmax, t.T);
     }
     const long slack = 16 * 1024 / 8;  // the loaders' whole 1 KB pieces past the last block
-    std::vector<double> coef((size_t)rows_total * NA + slack, 0.0);
-    parallel_for((long)tt.size(), [&](long t0, long t1) {
+    const size_t coef_n = (size_t)rows_total * NA + slack;
+    std::vector<double> coef;
+    if (src) coef.assign(coef_n, 0.0);
+    if (src) parallel_for((long)tt.size(), [&](long t0, long t1) {
         for (long ti = t0; ti < t1; ti++) {
             const LineTile &t = tt[ti];
             for (int p = 0; p < t.np; p++)
@@ -247,7 +271,7 @@ int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> 
                         const long v = i + off;
                         const long r = ((long)(t.k0 + p) * g.ny + j) * nx + i;
                         double *dst = coef.data() + (size_t)(t.cbase + v * P * t.nj + p * t.nj + l) * NA;
-                        for (int a = 0; a < NA; a++) dst[a] = src.c[(size_t)r * NA + a];
+                        for (int a = 0; a < NA; a++) dst[a] = src->c[(size_t)r * NA + a];
                     }
                 }
         }
@@ -264,8 +288,9 @@ int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> 
     ls.LV = LV;
     LSSP_HIP(hipMalloc(&ls.d_tiles, sizeof(LineTile) * tt.size()));
     LSSP_HIP(hipMemcpy(ls.d_tiles, tt.data(), sizeof(LineTile) * tt.size(), hipMemcpyHostToDevice));
-    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * coef.size()));
-    LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
+    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * coef_n));
+    if (src) LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef_n, hipMemcpyHostToDevice));
+    else LSSP_HIP(hipMemsetAsync(ls.d_coef, 0, sizeof(double) * coef_n, c->stream));
     LSSP_HIP(hipMalloc(&ls.d_claim, sizeof(unsigned long long)));
     LSSP_HIP(hipMemset(ls.d_claim, 0, sizeof(unsigned long long)));
     // claims in order of the tile's earliest start: a j-hop costs ~2 nj + 4
@@ -340,30 +365,15 @@ int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const std
     return LSSP_AMD_OK;
 }
 
-int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
-                   const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
-                   const std::vector<double> &Ux, LineILU &li)
+// Everything of the tiled k_linef sweeps that the grid alone decides: the
+// skewed columns' widths, the L tiles and their mirrored U tiles, the tiles off
+// the grid, both stream layouts, claim counters and order, the rhs streams
+// (zeroed) and the armed hand-off buffers.  The coefficient streams are
+// allocated here; cl / cu (host factors) fill them, or, both nullptr, they are
+// zeroed on the context's stream for launch_linefill_refill to write.
+static int build_linefill_tiles(lssp_amd_ctx *c, const LineGeom &g, const FillCoef *cl, const FillCoef *cu, LineILU &li)
 {
     using namespace lf;
-    LineGeom g;
-    if (!detect_fill1(n, Lp, Lj, Lx, Up, Uj, g)) return LSSP_AMD_EUNSUPPORTED;
-    {
-        const char *e = getenv("LSSP_AMD_LINEG");  // (read per build: tests select either path)
-        if (g.nz == 1 && g.ny <= G2_MAXNY && lineg_fits(g, 1) && !(e && !atoi(e))) {
-            const long pl = (long)g.nx * g.ny;
-            FillCoef fl, fu;
-            fl.build(Lp, Lj, Lx, false, n, g.nx, pl, g.unitL ? 6 : 7);
-            fu.build(Up, Uj, Ux, true, n, g.nx, pl, 7);
-            // k_lineg's components: S, SE, W (, diag) = FillCoef's 3, 4, 5 (, 6)
-            const int ncl = g.unitL ? 3 : 4;
-            std::vector<double> cl((size_t)n * ncl), cu((size_t)n * 4);
-            for (long r = 0; r < n; r++) {
-                for (int k = 0; k < ncl; k++) cl[r * ncl + k] = fl.c[r * fl.NA + 3 + k];
-                for (int k = 0; k < 4; k++) cu[r * 4 + k] = fu.c[r * fu.NA + 3 + k];
-            }
-            return build_lineg(c, g, 1, ncl, cl, cu, li);
-        }
-    }
     const int m = g.ny + g.nz - 1;
     const std::vector<int> wd = fill_widths(m);
     const int W = (int)wd.size(), S = (g.nz + P - 1) / P;
@@ -429,11 +439,7 @@ int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std
     };
     skip_off_grid(Lt);
     skip_off_grid(Ut);
-    const long pl = (long)g.nx * g.ny;
-    const int NAL = g.unitL ? 6 : 7;
-    FillCoef cl, cu;
-    cl.build(Lp, Lj, Lx, false, n, g.nx, pl, NAL);
-    cu.build(Up, Uj, Ux, true, n, g.nx, pl, 7);
+    const int NAL = g.unitL ? 6 : 7;  // (unit L: its diagonal is not streamed)
     li.g = g;
     li.kind = 1;
     li.P = P;
@@ -441,8 +447,8 @@ int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std
     li.LV = LV;
     li.W = W;
     li.S = S;
-    LSSP_TRY(fill_upload(c, g, Lt, W, cl, li.L));
-    LSSP_TRY(fill_upload(c, g, Ut, W, cu, li.U));
+    LSSP_TRY(fill_upload(c, g, Lt, W, cl, NAL, li.L));
+    LSSP_TRY(fill_upload(c, g, Ut, W, cu, 7, li.U));
     for (int K = 0; K < S; K++)
         for (int J = 0; J < W; J++) {
             LineTile &l = li.L.h_tiles[(size_t)K * W + J];
@@ -469,6 +475,47 @@ int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std
     LSSP_TRY(line_rearm(c, li));
     LSSP_HIP(hipStreamSynchronize(c->stream));
     return LSSP_AMD_OK;
+}
+
+int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
+                   const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
+                   const std::vector<double> &Ux, LineILU &li)
+{
+    LineGeom g;
+    if (!detect_fill1(n, Lp, Lj, Lx, Up, Uj, g)) return LSSP_AMD_EUNSUPPORTED;
+    const long pl = (long)g.nx * g.ny;
+    FillCoef cl, cu;
+    cl.build(Lp, Lj, Lx, false, n, g.nx, pl, g.unitL ? 6 : 7);
+    cu.build(Up, Uj, Ux, true, n, g.nx, pl, 7);
+    if (fill1_lineg_route(g)) {
+        // k_lineg's components: S, SE, W (, diag) = FillCoef's 3, 4, 5 (, 6)
+        const int ncl = g.unitL ? 3 : 4;
+        std::vector<double> sl((size_t)n * ncl), su((size_t)n * 4);
+        for (long r = 0; r < n; r++) {
+            for (int k = 0; k < ncl; k++) sl[r * ncl + k] = cl.c[r * cl.NA + 3 + k];
+            for (int k = 0; k < 4; k++) su[r * 4 + k] = cu.c[r * cu.NA + 3 + k];
+        }
+        return build_lineg(c, g, 1, ncl, sl, su, li);
+    }
+    return build_linefill_tiles(c, g, &cl, &cu, li);
+}
+
+// lssp_amd_iluk_create_dev: build_linefill would put the ILU(1) of the complete
+// nx x ny x nz box on the skewed tiles (not switched off, detect_fill1's sizes,
+// not the one-workgroup route) ...
+bool linefill_box_tiled(int nx, int ny, int nz)
+{
+    LineGeom g;
+    fill1_box_geom(nx, ny, nz, g);
+    return line_enabled() && fill1_sizes(nx, ny, nz) && !fill1_lineg_route(g);
+}
+// ... and those sweeps from the grid alone, coefficient streams zeroed
+int build_linefill_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li)
+{
+    if (!linefill_box_tiled(nx, ny, nz)) return LSSP_AMD_EUNSUPPORTED;
+    LineGeom g;
+    fill1_box_geom(nx, ny, nz, g);
+    return build_linefill_tiles(c, g, nullptr, nullptr, li);
 }
 
 // ---------------------------------------------------------------------------

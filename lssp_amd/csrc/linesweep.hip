@@ -308,7 +308,7 @@ static void line_plan(const LineGeom &, int &P, int &NJ, int &LV)
 // the two switches of the tiled route: LSSP_AMD_LINE=0 turns the line sweeps
 // off; a small 2-D grid (exam.cxx's 5-point Poisson) runs on one workgroup,
 // lines on lanes (linefill.hip k_lineg), unless LSSP_AMD_LINEG=0 keeps the tiles
-static bool line_enabled()
+bool line_enabled()
 {
     const char *env = getenv("LSSP_AMD_LINE");
     return !(env && !atoi(env));

@@ -347,6 +347,21 @@ class DILU:
         return cls(dev, h)
 
     @classmethod
+    def iluk_create_dev(cls, dev: Device, A: DMat, kind=ILUK, level=-1, tol=1e-3, p=-1, blk=0):
+        """create() for a matrix that lives in HBM, at the reference's default level too
+        (lssp_amd_iluk_create_dev): what create_dev() serves goes there unchanged; level 1 (or
+        < 0, the default) makes the ILU(1) of a complete natural-order 7-point box (nx, ny >= 3,
+        nz >= 2) or 5-point grid (nx, ny >= 3) on the skewed line sweeps, sweep_layout() ==
+        (2, 16, 8), on the device and bitwise create(level=1)'s handle; iluk_refactor() is
+        eligible on it at once.  Rows must be column-sorted.  ILUT, level >= 2, block-Jacobi,
+        nx == 2, a small 2-D grid on the one-workgroup sweeps, LSSP_AMD_LINE=0 and any matrix
+        that is no such box raise LsspError with status 6 (unsupported) and leave A as it was:
+        use create() there."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_iluk_create_dev(dev.h, A.h, kind, level, tol, p, blk, ctypes.byref(h)), "iluk_create_dev")
+        return cls(dev, h)
+
+    @classmethod
     def from_factors(cls, dev: Device, L, U):
         Lp, Lj, Lx = _i32(L[0]), _i32(L[1]), _f64(L[2])
         Up, Uj, Ux = _i32(U[0]), _i32(U[1]), _f64(U[2])
