@@ -366,11 +366,14 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      from the matrix handle without a host copy either
  *      (lssp_amd_ilu_create_dev, below), and so is the ILU(1) of such a box on
  *      the skewed line sweeps, the reference's default level
- *      (lssp_amd_iluk_create_dev).
+ *      (lssp_amd_iluk_create_dev).  ILUT of any one-block matrix with sorted
+ *      rows is factored on the device from the handle too
+ *      (lssp_amd_ilut_create_dev): the matrix stays in HBM, the finished
+ *      factors cross to the host once, where the sweeps' schedules are built.
  *      What still goes through the host: every other ILU setup
  *      (lssp_amd_ilu_create / lssp_amd_bilu_create take host arrays, as the
- *      reference factors on the host; download the CSR for them: ILUT, level
- *      >= 2, block-Jacobi, BILUK, general and small 2-D factors), and the
+ *      reference factors on the host; download the CSR for them: level
+ *      >= 2, block-Jacobi, BILUK, general and small 2-D ILUK factors), and the
  *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
  *      only when the PATTERN is new: new values on the same pattern stay on the
  *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor /
@@ -589,6 +592,40 @@ int lssp_amd_ilu_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, 
  * freed.  Returns when the stream has finished. */
 int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p,
                              int blk, lssp_amd_ilu **out);
+/* lssp_amd_ilu_create(kind ILUT) for a matrix that lives in HBM: ILUT(tol, p)
+ * (pc-ilut.cxx:51-286) is factored on the device, one wavefront per row, each
+ * row waiting per pivot for the earlier row it needs -- the reference's
+ * arithmetic in the reference's order, so the factors are its factors bit for
+ * bit.  tol < 0 means 1e-3, p <= 0 means ceil(nnz / n) (pc-ilut.cxx:436-438), as
+ * in lssp_amd_ilu_create.
+ * Host traffic: no array of A crosses to the host (two words of Ap and flag
+ * words come back).  The sweeps' packet schedules are built on the host from
+ * the factor pattern, so the finished L and U are downloaded once into the
+ * handle's host copies -- 12 B per factor entry, once -- and uploaded in
+ * schedule order as lssp_amd_ilu_create does.
+ * The handle is bitwise lssp_amd_ilu_create(LSSP_AMD_ILUT, ...)'s of the same
+ * matrix in lssp_amd_ilu_apply / _apply_async + _check / _trisolve /
+ * lssp_amd_solve, lssp_amd_ilu_info, _sweep_layout (0, 0, 0) and _get_factors;
+ * it owns what it needs, so A may be destroyed.  It is an ILUT handle: both
+ * refactor calls answer LSSP_AMD_EUNSUPPORTED for it.
+ * Eligible: A single-rank and square, one block (blk <= 0 or >= n), every row
+ * with strictly ascending columns inside [0, n) and its diagonal (checked on
+ * the device, nothing trusted; lssp_amd_csr_sort_columns_dev sorts), and no
+ * working row -- a row's L part or U part before the cut to p -- beyond
+ * lssp_amd_ilut_capacity() entries (1024).
+ * LSSP_AMD_EUNSUPPORTED with *out == NULL, nothing left allocated, A and ctx
+ * usable: a distributed A, block-Jacobi, an unsorted row or a repeated column,
+ * a missing diagonal (the reference inserts one first; that path is not
+ * reproduced here), a working row beyond the capacity; use lssp_amd_ilu_create
+ * for those.  NULL arguments or nrows != ncols: LSSP_AMD_EINVAL.  A bounded
+ * wait of the kernel expired: LSSP_AMD_ETIMEOUT.  A HIP error part-way:
+ * LSSP_AMD_EHIP, everything freed.  LSSP_AMD_SETUP_TIMES=1 prints the phases
+ * (check, numeric, compaction, download, schedules).  Returns when the stream
+ * has finished. */
+int lssp_amd_ilut_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, double tol, int p, int blk,
+                             lssp_amd_ilu **out);
+/* entries a working row of lssp_amd_ilut_create_dev may hold on each side of the diagonal */
+int lssp_amd_ilut_capacity(void);
 
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);

@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10700; }
+int lssp_amd_version(void) { return 10800; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -1181,6 +1181,70 @@ int lssp_amd_iluk_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, i
     if (level != 1 || !(blk <= 0 || blk >= A->nrows) || A->dist || A->nhalo > 0) return LSSP_AMD_EUNSUPPORTED;
     try {
         return iluk1_create_dev(c, A, kind, blk, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+// lssp_amd_ilu_create(kind ILUT) for a matrix in HBM: ilut_factor_lu's row loop
+// runs on the device, a wavefront per row (ilut_factor.hip), and
+// the finished L and U are downloaded once into the handle's host copies, from
+// which ilu_upload builds the sweeps' schedules exactly as ilu_create does --
+// the handle is the host-made one bit for bit.  No array of A crosses to the host.
+static int ilut_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, double tol, int p, int blk, lssp_amd_ilu **out)
+{
+    const int n = A->nrows, nnz = A->nnz;
+    if (!(blk <= 0 || blk >= n) || A->dist || A->nhalo > 0 || nnz < n) return LSSP_AMD_EUNSUPPORTED;
+    if (tol < 0) tol = 1e-3;
+    if (p <= 0) p = (int)(((long)nnz + n - 1) / n);  // pc-ilut.cxx:436-438
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    LSSP_HIP(hipSetDevice(c->device));
+    const double t_start = wall_time();
+    double t0 = t_start;
+    auto mark = [&](const char *phase) -> int {  // LSSP_AMD_SETUP_TIMES=1: the phases' own durations, the stream drained
+        if (!times) return LSSP_AMD_OK;
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        const double t = wall_time();
+        fprintf(stderr, "lssp_amd ilut_create_dev: %-12s %10.6f s\n", phase, t - t0);
+        t0 = t;
+        return LSSP_AMD_OK;
+    };
+    lssp_amd_ilu *M = new lssp_amd_ilu();
+    M->ctx = c;
+    M->n = n;
+    M->c_kind = LSSP_AMD_ILUT;
+    M->c_level = 0;
+    M->c_blk = blk;
+    int st;
+    try {
+        st = ilut_factor_dev(c, n, nnz, A->Ap, A->Aj, A->Ax, tol, p, M->Lp, M->Lj, M->Lx, M->Up, M->Uj, M->Ux, mark);
+        if (st == LSSP_AMD_OK) {
+            setup_mark(nullptr);
+            st = ilu_upload(c, M);
+        }
+        if (st == LSSP_AMD_OK) st = mark("schedules");
+    } catch (const std::exception &) {
+        st = LSSP_AMD_ENOMEM;
+    }
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);  // nothing of the handle is in flight when it is freed
+        lssp_amd_ilu_destroy(M);
+        return st;
+    }
+    M->setup_seconds = wall_time() - t_start;
+    *out = M;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_ilut_capacity(void) { return ilut_capacity(); }
+
+int lssp_amd_ilut_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, double tol, int p, int blk, lssp_amd_ilu **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !A || !out || A->nrows <= 0 || A->nrows != A->ncols) return LSSP_AMD_EINVAL;
+    try {
+        return ilut_create_dev(c, A, tol, p, blk, out);
     } catch (const std::exception &) {
         return LSSP_AMD_ENOMEM;
     }

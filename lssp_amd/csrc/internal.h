@@ -636,6 +636,18 @@ int refactor_plan_from_box(lssp_amd_ctx *c, int n, int nnz, const int *dAp, cons
 long fill1_nnz(int nx, int ny, int nz);
 int fill1_plan_pattern(lssp_amd_ctx *c, int n, int nx, int ny, int nz, RefactorPlan **out);
 int fill1_plan_levels(lssp_amd_ctx *c, RefactorPlan &p, int n, int nx, int ny, int nz);
+// lssp_amd_ilut_create_dev (ilut_factor.hip, ilut_dev.h): ILUT(tol,
+// p) of the one-block device CSR factored on the device, a wavefront per row,
+// and the finished factors downloaded into L* / U* (ilut_factor_lu's result bit
+// for bit).  EUNSUPPORTED: a row unsorted, with a repeated column or without
+// its diagonal, or a working row beyond ilut_capacity() entries on a side;
+// ETIMEOUT: a bounded wait expired.  mark(phase) is called after the check, the
+// numeric phase, the compaction and the download.
+int ilut_capacity();
+int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, const double *dAx, double tol,
+                    int p, std::vector<int> &Lp, std::vector<int> &Lj, std::vector<double> &Lx,
+                    std::vector<int> &Up, std::vector<int> &Uj, std::vector<double> &Ux,
+                    const std::function<int(const char *)> &mark);
 // linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
 // the factored values Fx on the pattern (Fp, Fj); every slot is written
 int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);

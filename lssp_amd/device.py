@@ -362,6 +362,24 @@ class DILU:
         return cls(dev, h)
 
     @classmethod
+    def ilut_create_dev(cls, dev: Device, A: DMat, tol=1e-3, p=-1, blk=0):
+        """create(kind=ILUT) for a matrix that lives in HBM (lssp_amd_ilut_create_dev): ILUT(tol,
+        p) factored on the device, a wavefront per row, bitwise create()'s handle.  A's arrays
+        stay in HBM; the finished factors are downloaded once, for the sweeps' schedules.  Rows
+        must be column-sorted and hold their diagonal.  Block-Jacobi, an unsorted row, a repeated
+        column, a missing diagonal and a working row beyond ilut_capacity() entries on a side
+        raise LsspError with status 6 (unsupported) and leave A as it was: use create() there."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_ilut_create_dev(dev.h, A.h, tol, p, blk, ctypes.byref(h)), "ilut_create_dev")
+        return cls(dev, h)
+
+    @staticmethod
+    def ilut_capacity() -> int:
+        """entries a working row of ilut_create_dev() may hold on each side of the diagonal"""
+        from . import _lib
+        return _lib.load().lssp_amd_ilut_capacity()
+
+    @classmethod
     def from_factors(cls, dev: Device, L, U):
         Lp, Lj, Lx = _i32(L[0]), _i32(L[1]), _f64(L[2])
         Up, Uj, Ux = _i32(U[0]), _i32(U[1]), _f64(U[2])
