@@ -193,6 +193,42 @@ int lssp_amd_ilu_get_factors(const lssp_amd_ilu *M, int *Lp, int *Lj, double *Lx
  * (*lines = 16 lines of j + k, *planes = 8); 0 (and 0 x 0) for the general
  * packet sweeps.  Any pointer may be NULL. */
 int lssp_amd_ilu_sweep_layout(const lssp_amd_ilu *M, int *line, int *lines, int *planes);
+/* lssp_amd_ilu_from_factors for factors that already live in HBM (no reference
+ * counterpart): dLp .. dUx are DEVICE arrays in the same layout (L: diagonal
+ * LAST per row; U: pivot FIRST).  No factor array crosses to the host: both
+ * packet schedules are built on the device, and only a few
+ * words come back (Lp[n], Up[n], flags and counts).  The handle owns device-
+ * to-device copies, so the caller may free or reuse its arrays on return; its
+ * host copies are made by the first call that reads them
+ * (lssp_amd_ilu_get_factors, lssp_amd_ilu_trisolve).  The handle always runs
+ * the packet sweeps -- lssp_amd_ilu_sweep_layout answers (0, 0, 0) even for a
+ * grid's ILU(0) -- and every sweep is bitwise the reference's, so results do
+ * not depend on that: lssp_amd_ilu_apply / _apply_async + _check / _trisolve /
+ * lssp_amd_solve / _info / _get_factors are bitwise those of
+ * lssp_amd_ilu_from_factors on the same arrays, and both refactor calls
+ * answer LSSP_AMD_EUNSUPPORTED, as there.  LSSP_AMD_EUNSUPPORTED, with *out
+ * NULL and nothing left allocated: a strict row beyond 24 entries, more than
+ * 4096 packets in one block of the schedule, a record or index stream beyond
+ * INT_MAX words (the sync-free fallback is not built on the device: use
+ * lssp_amd_ilu_from_factors there).  LSSP_AMD_EINVAL: a NULL argument,
+ * n <= 0, a row without a diagonal slot, a strict column on the wrong side of
+ * its row or outside [0, n).  LSSP_AMD_ETIMEOUT: a bounded wait of the level
+ * pass expired.  LSSP_AMD_EHIP: a HIP error, everything freed. */
+int lssp_amd_ilu_from_factors_dev(lssp_amd_ctx *ctx, int n, const int *dLp, const int *dLj, const double *dLx,
+                                  const int *dUp, const int *dUj, const double *dUx, lssp_amd_ilu **out);
+/* The packet schedule an apply of M walks (no reference counterpart: a query
+ * like lssp_amd_ilu_sweep_layout).  which = 0: the L sweep's, 1: the U
+ * sweep's.  hdr = {B (rows per block), nb (blocks), nsteps, npackets, EP
+ * (operand slots per row: 4, 8, 16, 24), EXT (HBM operand loads per loader
+ * lane), rows per packet, rec words, idx words, unit (every diagonal is 1.0),
+ * nlevels, origin}; origin = 0: built on the host, 1: on the device.  With
+ * every array pointer NULL only hdr is filled (the two-call form of
+ * lssp_amd_csr_to_bcsr); otherwise each non-NULL array is downloaded: blk
+ * (nb + 1), desc (4 * npackets), rec (rec words), idx (idx words), perm and
+ * pos (n).  A handle without a packet schedule (line sweeps, the sync-free
+ * fallback), or a record stream beyond INT_MAX words: LSSP_AMD_EUNSUPPORTED. */
+int lssp_amd_ilu_get_schedule(const lssp_amd_ilu *M, int which, int hdr[12], int *blk, int *desc,
+                              unsigned *rec, int *idx, int *perm, int *pos);
 
 /* ---- BILUK: block ILU(level) on bs x bs blocks (lssp_pc_biluk_assemble,
  *      pc-biluk.cxx:388-431; the reference passes num_blks = n / bs).  The apply
@@ -368,8 +404,10 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      the skewed line sweeps, the reference's default level
  *      (lssp_amd_iluk_create_dev).  ILUT of any one-block matrix with sorted
  *      rows is factored on the device from the handle too
- *      (lssp_amd_ilut_create_dev): the matrix stays in HBM, the finished
- *      factors cross to the host once, where the sweeps' schedules are built.
+ *      (lssp_amd_ilut_create_dev): the matrix and the finished factors stay
+ *      in HBM, where the sweeps' schedules are built too; factors that
+ *      already live in HBM make a handle the same way
+ *      (lssp_amd_ilu_from_factors_dev).
  *      What still goes through the host: every other ILU setup
  *      (lssp_amd_ilu_create / lssp_amd_bilu_create take host arrays, as the
  *      reference factors on the host; download the CSR for them: level
@@ -599,10 +637,14 @@ int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind,
  * bit.  tol < 0 means 1e-3, p <= 0 means ceil(nnz / n) (pc-ilut.cxx:436-438), as
  * in lssp_amd_ilu_create.
  * Host traffic: no array of A crosses to the host (two words of Ap and flag
- * words come back).  The sweeps' packet schedules are built on the host from
- * the factor pattern, so the finished L and U are downloaded once into the
- * handle's host copies -- 12 B per factor entry, once -- and uploaded in
- * schedule order as lssp_amd_ilu_create does.
+ * words come back), and no array of the factors: the finished L and U stay
+ * in HBM and the sweeps' packet schedules are built on the device, byte for
+ * byte as lssp_amd_ilu_create builds them (lssp_amd_ilu_from_factors_dev's
+ * builder; lssp_amd_ilu_get_schedule answers origin 1); the handle's host
+ * copies are made by the first call that reads them.  Factors beyond that
+ * builder (p > 24 entries in a strict row, the packet limits) are downloaded
+ * once, 12 B per entry, and scheduled on the host as before version 1.9;
+ * LSSP_AMD_SCHED_HOST=1 forces that route.
  * The handle is bitwise lssp_amd_ilu_create(LSSP_AMD_ILUT, ...)'s of the same
  * matrix in lssp_amd_ilu_apply / _apply_async + _check / _trisolve /
  * lssp_amd_solve, lssp_amd_ilu_info, _sweep_layout (0, 0, 0) and _get_factors;
@@ -620,8 +662,9 @@ int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind,
  * for those.  NULL arguments or nrows != ncols: LSSP_AMD_EINVAL.  A bounded
  * wait of the kernel expired: LSSP_AMD_ETIMEOUT.  A HIP error part-way:
  * LSSP_AMD_EHIP, everything freed.  LSSP_AMD_SETUP_TIMES=1 prints the phases
- * (check, numeric, compaction, download, schedules).  Returns when the stream
- * has finished. */
+ * (check, numeric, compaction, then per side check, levels, order, entries,
+ * packets, fill; on the host route download, schedules).  Returns when the
+ * stream has finished. */
 int lssp_amd_ilut_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, double tol, int p, int blk,
                              lssp_amd_ilu **out);
 /* entries a working row of lssp_amd_ilut_create_dev may hold on each side of the diagonal */

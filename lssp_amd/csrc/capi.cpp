@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10800; }
+int lssp_amd_version(void) { return 10900; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -1188,9 +1188,11 @@ int lssp_amd_iluk_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, i
 
 // lssp_amd_ilu_create(kind ILUT) for a matrix in HBM: ilut_factor_lu's row loop
 // runs on the device, a wavefront per row (ilut_factor.hip), and
-// the finished L and U are downloaded once into the handle's host copies, from
-// which ilu_upload builds the sweeps' schedules exactly as ilu_create does --
-// the handle is the host-made one bit for bit.  No array of A crosses to the host.
+// the finished L and U stay in HBM, where the device schedule builder
+// (tri_sched.hip) makes the sweeps' schedules byte for byte as
+// ilu_upload makes them from host copies -- the handle is the host-made one bit
+// for bit, its host copies made by their first reader.  What the device builder
+// refuses takes the download and ilu_upload.  No array of A crosses to the host.
 static int ilut_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, double tol, int p, int blk, lssp_amd_ilu **out)
 {
     const int n = A->nrows, nnz = A->nnz;
@@ -1217,12 +1219,38 @@ static int ilut_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, double tol, i
     M->c_blk = blk;
     int st;
     try {
-        st = ilut_factor_dev(c, n, nnz, A->Ap, A->Aj, A->Ax, tol, p, M->Lp, M->Lj, M->Lx, M->Up, M->Uj, M->Ux, mark);
-        if (st == LSSP_AMD_OK) {
+        // LSSP_AMD_SCHED_HOST=1: the schedules built on the host from a download, as before 1.9 (A/B)
+        const bool host_route = getenv("LSSP_AMD_SCHED_HOST") && atoi(getenv("LSSP_AMD_SCHED_HOST"));  // read per call
+        IlutDevFactors F;
+        st = ilut_factor_dev(c, n, nnz, A->Ap, A->Aj, A->Ax, tol, p, M->Lp, M->Lj, M->Lx, M->Up, M->Uj, M->Ux, mark,
+                             host_route ? nullptr : &F);
+        bool upload = host_route;
+        if (st == LSSP_AMD_OK && !host_route) {
+            // the finished factors stay in HBM and go through the device schedule
+            // builder (tri_sched.hip); the host copies are made by their first reader
+            M->fd_Lp = F.Lp, M->fd_Lj = F.Lj, M->fd_Lx = F.Lx, M->fd_Up = F.Up, M->fd_Uj = F.Uj, M->fd_Ux = F.Ux;
+            M->dev_nnzL = F.nnzL;
+            M->dev_nnzU = F.nnzU;
+            M->host_missing = M->host_stale = true;
+            st = build_trisched_dev(c, n, F.nnzL, F.Lp, F.Lj, F.Lx, false, nullptr, M->lower, mark);
+            if (st == LSSP_AMD_OK)
+                st = build_trisched_dev(c, n, F.nnzU, F.Up, F.Uj, F.Ux, true, M->lower.bp_pos, M->upper, mark);
+            if (st == LSSP_AMD_EUNSUPPORTED) {
+                // beyond the device builder (a strict row beyond 24 entries, the packet
+                // limits): the download and the host schedules, sync-free fallback included
+                (void)hipStreamSynchronize(c->stream);
+                free_trisched(M->lower);
+                free_trisched(M->upper);
+                st = refactor_host_factors(M);
+                if (st == LSSP_AMD_OK) st = mark("download");
+                upload = true;
+            }
+        }
+        if (st == LSSP_AMD_OK && upload) {
             setup_mark(nullptr);
             st = ilu_upload(c, M);
+            if (st == LSSP_AMD_OK) st = mark("schedules");
         }
-        if (st == LSSP_AMD_OK) st = mark("schedules");
     } catch (const std::exception &) {
         st = LSSP_AMD_ENOMEM;
     }
@@ -1274,6 +1302,110 @@ static int ilu_from_factors(lssp_amd_ctx *c, int n, const int *Lp, const int *Lj
     }
     M->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     *out = M;
+    return LSSP_AMD_OK;
+}
+
+// lssp_amd_ilu_from_factors for factors that live in HBM: the
+// handle copies the six arrays device to device, both packet schedules are built
+// on the device from the copies (tri_sched.hip), and the host copies are made by
+// the first call that reads them (refactor_host_factors).  The handle always
+// runs the packet sweeps: no line-sweep detection, no sync-free fallback.
+static int ilu_from_factors_dev(lssp_amd_ctx *c, int n, const int *dLp, const int *dLj, const double *dLx,
+                                const int *dUp, const int *dUj, const double *dUx, lssp_amd_ilu **out)
+{
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    LSSP_HIP(hipSetDevice(c->device));
+    const double t_start = wall_time();
+    double t0 = t_start;
+    auto mark = [&](const char *phase) -> int {  // LSSP_AMD_SETUP_TIMES=1: the phases' own durations, the stream drained
+        if (!times) return LSSP_AMD_OK;
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        const double t = wall_time();
+        fprintf(stderr, "lssp_amd from_factors_dev: %-12s %10.6f s\n", phase, t - t0);
+        t0 = t;
+        return LSSP_AMD_OK;
+    };
+    int h_n[4] = {0, 0, 0, 0};  // Lp[0], Lp[n], Up[0], Up[n]
+    LSSP_HIP(hipMemcpyAsync(h_n + 0, dLp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h_n + 1, dLp + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h_n + 2, dUp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h_n + 3, dUp + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    if (h_n[0] != 0 || h_n[2] != 0 || h_n[1] < n || h_n[3] < n) return LSSP_AMD_EINVAL;  // (a diagonal slot per row)
+    lssp_amd_ilu *M = new lssp_amd_ilu();
+    M->ctx = c;
+    M->n = n;
+    M->host_missing = M->host_stale = true;
+    M->dev_nnzL = h_n[1];
+    M->dev_nnzU = h_n[3];
+    auto build = [&]() -> int {
+        auto copy = [&](auto *&d, const auto *src, size_t cnt) -> int {
+            using T = typename std::remove_const<typename std::remove_pointer<decltype(src)>::type>::type;
+            LSSP_HIP(hipMalloc(&d, sizeof(T) * std::max<size_t>(cnt, 1)));
+            LSSP_HIP(hipMemcpyAsync(d, src, sizeof(T) * cnt, hipMemcpyDeviceToDevice, c->stream));
+            return LSSP_AMD_OK;
+        };
+        LSSP_TRY(copy(M->fd_Lp, dLp, (size_t)n + 1));
+        LSSP_TRY(copy(M->fd_Lj, dLj, (size_t)h_n[1]));
+        LSSP_TRY(copy(M->fd_Lx, dLx, (size_t)h_n[1]));
+        LSSP_TRY(copy(M->fd_Up, dUp, (size_t)n + 1));
+        LSSP_TRY(copy(M->fd_Uj, dUj, (size_t)h_n[3]));
+        LSSP_TRY(copy(M->fd_Ux, dUx, (size_t)h_n[3]));
+        LSSP_TRY(mark("copies"));
+        LSSP_TRY(build_trisched_dev(c, n, h_n[1], M->fd_Lp, M->fd_Lj, M->fd_Lx, false, nullptr, M->lower, mark));
+        LSSP_TRY(build_trisched_dev(c, n, h_n[3], M->fd_Up, M->fd_Uj, M->fd_Ux, true, M->lower.bp_pos, M->upper, mark));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        return LSSP_AMD_OK;
+    };
+    const int st = build();
+    if (st != LSSP_AMD_OK) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);  // nothing of the handle is in flight when it is freed
+        lssp_amd_ilu_destroy(M);
+        return st;
+    }
+    M->setup_seconds = wall_time() - t_start;
+    *out = M;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_ilu_from_factors_dev(lssp_amd_ctx *c, int n, const int *dLp, const int *dLj, const double *dLx,
+                                  const int *dUp, const int *dUj, const double *dUx, lssp_amd_ilu **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !out || n <= 0 || !dLp || !dLj || !dLx || !dUp || !dUj || !dUx) return LSSP_AMD_EINVAL;
+    try {
+        return ilu_from_factors_dev(c, n, dLp, dLj, dLx, dUp, dUj, dUx, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+int lssp_amd_ilu_get_schedule(const lssp_amd_ilu *M, int which, int hdr[12], int *blk, int *desc, unsigned *rec,
+                              int *idx, int *perm, int *pos)
+{
+    if (!M || !hdr || (which != 0 && which != 1)) return LSSP_AMD_EINVAL;
+    // line sweeps and the sync-free fallback have no packet schedule
+    if (M->line.ntiles > 0 || !(M->lower.pk6_n > 0 && M->upper.pk6_n > 0)) return LSSP_AMD_EUNSUPPORTED;
+    const lssp_amd::TriSched &t = which ? M->upper : M->lower;
+    if (t.pk6_nrec > INT_MAX || t.pk6_nidx > INT_MAX) return LSSP_AMD_EUNSUPPORTED;  // hdr holds ints
+    const int h[12] = {t.bp_B,     t.bp_nb,         t.bp_nsteps,     t.pk6_n,   t.pk6_ep,  t.pk6_ext,
+                       t.pk6_rows, (int)t.pk6_nrec, (int)t.pk6_nidx, t.bp_unit, t.nlevels, t.bp_origin};
+    memcpy(hdr, h, sizeof(h));
+    if (!blk && !desc && !rec && !idx && !perm && !pos) return LSSP_AMD_OK;
+    lssp_amd_ctx *c = M->ctx;
+    LSSP_HIP(hipSetDevice(c->device));
+    auto down = [&](auto *dst, const auto *src, size_t cnt) -> int {
+        if (dst) LSSP_HIP(hipMemcpyAsync(dst, src, sizeof(*dst) * cnt, hipMemcpyDeviceToHost, c->stream));
+        return LSSP_AMD_OK;
+    };
+    LSSP_TRY(down(blk, t.pk6_blk, (size_t)t.bp_nb + 1));
+    LSSP_TRY(down(desc, t.pk6_desc, std::max<size_t>(4 * (size_t)t.pk6_n, 1)));
+    LSSP_TRY(down(rec, t.pk6_rec, (size_t)t.pk6_nrec));
+    LSSP_TRY(down(idx, t.pk6_idx, (size_t)t.pk6_nidx));
+    LSSP_TRY(down(perm, t.bp_perm, (size_t)M->n));
+    LSSP_TRY(down(pos, t.bp_pos, (size_t)M->n));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
     return LSSP_AMD_OK;
 }
 
@@ -1507,6 +1639,9 @@ int lssp_amd_ilu_destroy(lssp_amd_ilu *M)
     for (double *p : M->d_sh)
         if (p) (void)hipFree(p);
     if (M->d_rperm) (void)hipFree(M->d_rperm);
+    for (void *q : {(void *)M->fd_Lp, (void *)M->fd_Lj, (void *)M->fd_Lx, (void *)M->fd_Up, (void *)M->fd_Uj,
+                    (void *)M->fd_Ux})
+        if (q) (void)hipFree(q);
     if (M->d_Dinv) (void)hipFree(M->d_Dinv);
     if (M->d_mid) (void)hipFree(M->d_mid);
     delete M;

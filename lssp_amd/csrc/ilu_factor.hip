@@ -557,6 +557,33 @@ int refactor_levels(lssp_amd_ctx *c, RefactorPlan &p, int n)
 int refactor_host_factors(lssp_amd_ilu *M)
 {
     if (M->brf) return bilu_refactor_host_factors(M);  // a BILUK handle (lssp_amd_bilu_refactor)
+    if (M->host_missing && M->fd_Lp) {
+        // a handle made from factors in HBM: its device copies come down once, then go
+        lssp_amd_ctx *c = M->ctx;
+        const size_t n1 = (size_t)M->n + 1, nl = (size_t)M->dev_nnzL, nu = (size_t)M->dev_nnzU;
+        std::vector<int> Lp(n1), Lj(nl), Up(n1), Uj(nu);
+        std::vector<double> Lx(nl), Ux(nu);
+        LSSP_HIP(hipMemcpyAsync(Lp.data(), M->fd_Lp, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Lj.data(), M->fd_Lj, sizeof(int) * nl, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Lx.data(), M->fd_Lx, sizeof(double) * nl, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Up.data(), M->fd_Up, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Uj.data(), M->fd_Uj, sizeof(int) * nu, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Ux.data(), M->fd_Ux, sizeof(double) * nu, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        M->Lp = std::move(Lp);
+        M->Lj = std::move(Lj);
+        M->Lx = std::move(Lx);
+        M->Up = std::move(Up);
+        M->Uj = std::move(Uj);
+        M->Ux = std::move(Ux);
+        for (void *q : {(void *)M->fd_Lp, (void *)M->fd_Lj, (void *)M->fd_Lx, (void *)M->fd_Up, (void *)M->fd_Uj,
+                        (void *)M->fd_Ux})
+            (void)hipFree(q);
+        M->fd_Lp = M->fd_Lj = M->fd_Up = M->fd_Uj = nullptr;
+        M->fd_Lx = M->fd_Ux = nullptr;
+        M->host_missing = M->host_stale = false;
+        return LSSP_AMD_OK;
+    }
     if (!M->host_stale || !M->rf) return LSSP_AMD_OK;
     lssp_amd_ctx *c = M->ctx;
     const int n = M->n;

@@ -10,9 +10,10 @@
 // steps, which tools/ilut_dev_check.cpp runs on the host.
 //
 // Phases: eligibility check (k_ilut_check) -> numeric (k_ilut into per-row
-// staging areas) -> compaction (counts, exclusive scan, k_ilut_pack) -> download
-// of the finished L and U (12 B per factor entry, once: the packet schedules are
-// built on the host from the factor pattern, ilu_upload / tri_bp.cpp).  No array
+// staging areas) -> compaction (counts, exclusive scan, k_ilut_pack).  The
+// finished L and U then stay in HBM for the device schedule builder
+// (tri_sched.hip), or -- on the host schedule route -- are
+// downloaded once (12 B per factor entry) for ilu_upload / tri_bp.cpp.  No array
 // of the matrix crosses to the host.
 #include <hip/hip_runtime.h>
 
@@ -428,7 +429,7 @@ int ilut_capacity() { return ILUT_CAP_LARGE; }
 int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, const double *dAx, double tol,
                     int p, std::vector<int> &Lp, std::vector<int> &Lj, std::vector<double> &Lx,
                     std::vector<int> &Up, std::vector<int> &Uj, std::vector<double> &Ux,
-                    const std::function<int(const char *)> &mark)
+                    const std::function<int(const char *)> &mark, IlutDevFactors *keep)
 {
     if (n < 1 || nnz < n) return LSSP_AMD_EUNSUPPORTED;
     DevBufs B;
@@ -506,12 +507,11 @@ int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *
     LSSP_HIP(B.get(&tmp, bytes));
     LSSP_HIP(rocprim::exclusive_scan(tmp, bytes, cl, dLp, 0, (size_t)n + 1, rocprim::plus<int>(), c->stream));
     LSSP_HIP(rocprim::exclusive_scan(tmp, bytes, cu, dUp, 0, (size_t)n + 1, rocprim::plus<int>(), c->stream));
-    Lp.resize((size_t)n + 1);
-    Up.resize((size_t)n + 1);
-    LSSP_HIP(hipMemcpyAsync(Lp.data(), dLp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
-    LSSP_HIP(hipMemcpyAsync(Up.data(), dUp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
+    int h_nnz[2] = {0, 0};
+    LSSP_HIP(hipMemcpyAsync(h_nnz, dLp + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h_nnz + 1, dUp + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));
-    const size_t nnzL = (size_t)Lp[n], nnzU = (size_t)Up[n];
+    const size_t nnzL = (size_t)h_nnz[0], nnzU = (size_t)h_nnz[1];
     int *dLj = nullptr, *dUj = nullptr;
     double *dLx = nullptr, *dUx = nullptr;
     LSSP_HIP(B.get(&dLj, nnzL));
@@ -522,6 +522,18 @@ int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *
     LSSP_HIP(hipGetLastError());
     LSSP_TRY(mark("compaction"));
 
+    if (keep) {  // the factors stay in HBM: the caller owns the six arrays from here on
+        void *six[6] = {dLp, dLj, dLx, dUp, dUj, dUx};
+        B.all.erase(std::remove_if(B.all.begin(), B.all.end(),
+                                   [&](void *q) { return std::find(six, six + 6, q) != six + 6; }),
+                    B.all.end());
+        *keep = IlutDevFactors{dLp, dLj, dUp, dUj, dLx, dUx, (int)nnzL, (int)nnzU};
+        return LSSP_AMD_OK;
+    }
+    Lp.resize((size_t)n + 1);
+    Up.resize((size_t)n + 1);
+    LSSP_HIP(hipMemcpyAsync(Lp.data(), dLp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(Up.data(), dUp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
     Lj.resize(nnzL);
     Lx.resize(nnzL);
     Uj.resize(nnzU);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/lssp_amd.h"
+#include "sched_dev.h"  // BP_RING, PK3_*, pk6_xs_off: shared with the device schedule builder
 
 namespace lssp_amd {
 
@@ -212,11 +213,12 @@ struct TriSched {
     mutable unsigned long long pk6_base = 0;
     unsigned long long *pk6_claim = nullptr;
     std::vector<int> h_pos;  // L factor: row -> schedule position (for the U factor's build)
+    // lssp_amd_ilu_get_schedule: the streams' lengths in 4-byte words (trailing words included), whether every
+    // diagonal is exactly 1.0 (unit above is set with the sync-free arrays only), and who built the schedule
+    // (0: tri_bp.cpp on the host, 1: tri_sched.hip on the device)
+    long pk6_nrec = 0, pk6_nidx = 0;
+    int bp_unit = 0, bp_origin = 0;
 };
-constexpr int PK3_ROWS = 256;    // v6: rows per packet = compute lanes = loader lanes
-constexpr int PK3_EXT = 4;       // v6: HBM x operands per packet row, at most (on average; the kernel
-                                 // runs 2, 3 or 4 loads per lane, TriSched::pk6_ext; 2 before round 6)
-constexpr int PK3_CAP = 4096;    // v6: packets per block (descriptors staged in LDS)
 
 // ---- line sweeps of structured ILU(0) factors (linesweep.hip) ----------------
 // A tile is 256 / P lines x P planes = 256 rows per step, P in {4, 8, 16}
@@ -365,6 +367,11 @@ struct lssp_amd_ilu {
     // until then the entry counts are these
     bool host_missing = false;
     int dev_nnzL = 0, dev_nnzU = 0;
+    // made by lssp_amd_ilu_from_factors_dev (and by lssp_amd_ilut_create_dev on the device schedule
+    // route): the handle's own device copies of the factors, from which refactor_host_factors makes the
+    // host copies on first use (and frees these); nullptr otherwise
+    int *fd_Lp = nullptr, *fd_Lj = nullptr, *fd_Up = nullptr, *fd_Uj = nullptr;
+    double *fd_Lx = nullptr, *fd_Ux = nullptr;
 };
 
 namespace lssp_amd {
@@ -448,19 +455,18 @@ int launch_finalize(lssp_amd_ctx *c, const double *sums, int nslot, const Fin &f
 int launch_fill(lssp_amd_ctx *c, double *x, long n, uint64_t bits);
 int launch_trisolve(lssp_amd_ctx *c, const TriSched &t, const double *rhs, double *x,
                     double *reset);
-constexpr int BP_RING = 4096;  // LDS ring of recently computed values (32 KB)
-// k_tri_pk6's LDS operand array: the value ring [0, BP_RING), a +0.0 pad slot
-// at BP_RING, then the two buffers of landed HBM operands (PK3_EXT per packet
-// row of 256).  Byte offset of entry base + par * buffer + k:
-constexpr int pk6_xs_off(int base, int par, int k) { return 8 * (base + par * 256 * PK3_EXT + k); }
+// BP_RING, pk6_xs_off: sched_dev.h
 int build_bp_schedule(lssp_amd_ctx *c, int n, const std::vector<int> &Tp, const std::vector<int> &Tj,
                       const std::vector<double> &Tx, bool upper, const std::vector<int> &lev,
                       TriSched &t, const TriSched *prod = nullptr);
-int build_packets6(int n, const std::vector<int> &perm, const std::vector<int> &pos, const std::vector<int> &rp,
-                   const int *cols, const double *vals,
-                   const std::vector<double> &diag, bool unit, const std::vector<int> &step_pos,
-                   const std::vector<int> &blk_step, int nb, long B, const std::vector<int> &rhs_index,
-                   TriSched &t);
+// tri_sched.hip: the same schedule from a factor in HBM (device CSR Tp / Tj / Tx of nnz
+// entries), byte for byte; rhs_pos: the L sweep's bp_pos for the U factor (nullptr: the factor's own).
+// EINVAL: malformed (tri_levels' rules); EUNSUPPORTED: a strict row beyond 24 entries, more than PK3_CAP
+// packets in a block, a stream beyond INT_MAX words (the host builder falls back to the sync-free sweep
+// there; this one does not); ETIMEOUT: a bounded wait of the level pass expired.  t is left for
+// free_trisched on every failure.  mark(phase) is called after each stage.
+int build_trisched_dev(lssp_amd_ctx *c, int n, int nnz, const int *dTp, const int *dTj, const double *dTx, bool upper,
+                       const int *rhs_pos, TriSched &t, const std::function<int(const char *)> &mark);
 int launch_ilu_apply(lssp_amd_ctx *c, const lssp_amd_ilu *M, double *x, const double *rhs);
 int launch_pack(lssp_amd_ctx *c, const int *idx, const double *x, double *buf, int n);
 int launch_sum_ranks(lssp_amd_ctx *c, int nslot, const Fin &f);
@@ -642,12 +648,19 @@ int fill1_plan_levels(lssp_amd_ctx *c, RefactorPlan &p, int n, int nx, int ny, i
 // for bit).  EUNSUPPORTED: a row unsorted, with a repeated column or without
 // its diagonal, or a working row beyond ilut_capacity() entries on a side;
 // ETIMEOUT: a bounded wait expired.  mark(phase) is called after the check, the
-// numeric phase, the compaction and the download.
+// numeric phase, the compaction and the download.  keep != nullptr: no download
+// -- the finished factors stay in HBM, the six arrays handed to the caller
+// (hipFree), L* / U* left empty.
+struct IlutDevFactors {
+    int *Lp = nullptr, *Lj = nullptr, *Up = nullptr, *Uj = nullptr;
+    double *Lx = nullptr, *Ux = nullptr;
+    int nnzL = 0, nnzU = 0;
+};
 int ilut_capacity();
 int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, const double *dAx, double tol,
                     int p, std::vector<int> &Lp, std::vector<int> &Lj, std::vector<double> &Lx,
                     std::vector<int> &Up, std::vector<int> &Uj, std::vector<double> &Ux,
-                    const std::function<int(const char *)> &mark);
+                    const std::function<int(const char *)> &mark, IlutDevFactors *keep = nullptr);
 // linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
 // the factored values Fx on the pattern (Fp, Fj); every slot is written
 int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);

@@ -365,7 +365,8 @@ class DILU:
     def ilut_create_dev(cls, dev: Device, A: DMat, tol=1e-3, p=-1, blk=0):
         """create(kind=ILUT) for a matrix that lives in HBM (lssp_amd_ilut_create_dev): ILUT(tol,
         p) factored on the device, a wavefront per row, bitwise create()'s handle.  A's arrays
-        stay in HBM; the finished factors are downloaded once, for the sweeps' schedules.  Rows
+        stay in HBM, and so do the finished factors: the sweeps' schedules are built on the device
+        (schedule(w)["origin"] == 1) and factors() downloads them on first use.  Rows
         must be column-sorted and hold their diagonal.  Block-Jacobi, an unsorted row, a repeated
         column, a missing diagonal and a working row beyond ilut_capacity() entries on a side
         raise LsspError with status 6 (unsupported) and leave A as it was: use create() there."""
@@ -387,6 +388,43 @@ class DILU:
         _ck(dev.L.lssp_amd_ilu_from_factors(dev.h, Lp.size - 1, _p(Lp), _p(Lj), _p(Lx), _p(Up), _p(Uj), _p(Ux),
                                             ctypes.byref(h)), "ilu_from_factors")
         return cls(dev, h)
+
+    @classmethod
+    def from_factors_dev(cls, dev: Device, L, U):
+        """from_factors() for factors that live in HBM (lssp_amd_ilu_from_factors_dev): L and U are
+        (DIdx, DIdx, DVec) triples, L with its diagonal last in each row, U with its pivot first.
+        Both packet schedules are built on the device; no factor array crosses to the host, and
+        the handle owns copies, so the arrays may be freed.  Always on the packet sweeps
+        (sweep_layout() == (0, 0, 0)); bitwise from_factors() otherwise.  A strict row beyond 24
+        entries or a schedule beyond the packet limits raises LsspError with status 6
+        (unsupported): use from_factors() there; malformed factors raise status 1."""
+        n = L[0].n - 1
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_ilu_from_factors_dev(dev.h, n, L[0].ptr, L[1].ptr, L[2].ptr, U[0].ptr, U[1].ptr, U[2].ptr,
+                                                ctypes.byref(h)), "ilu_from_factors_dev")
+        return cls(dev, h)
+
+    _SCHED_HDR = ("B", "nb", "nsteps", "npackets", "EP", "EXT", "rows", "rec_words", "idx_words", "unit", "nlevels",
+                  "origin")
+
+    def schedule(self, which: int):
+        """The packet schedule of the L (which = 0) or U (1) sweep (lssp_amd_ilu_get_schedule): a
+        dict of the header fields (B, nb, nsteps, npackets, EP, EXT, rows, rec_words, idx_words,
+        unit, nlevels, origin -- 0 built on the host, 1 on the device) and the arrays blk, desc,
+        rec, idx, perm, pos.  A handle on line sweeps or on the sync-free fallback raises
+        LsspError with status 6 (unsupported)."""
+        hdr = np.zeros(12, np.int32)
+        _ck(self.dev.L.lssp_amd_ilu_get_schedule(self.h, which, _p(hdr), None, None, None, None, None, None),
+            "ilu_get_schedule")
+        s = dict(zip(self._SCHED_HDR, (int(v) for v in hdr)))
+        s["blk"] = np.zeros(s["nb"] + 1, np.int32)
+        s["desc"] = np.zeros(max(4 * s["npackets"], 1), np.int32)
+        s["rec"] = np.zeros(s["rec_words"], np.uint32)
+        s["idx"] = np.zeros(s["idx_words"], np.int32)
+        s["perm"], s["pos"] = np.zeros(self.n, np.int32), np.zeros(self.n, np.int32)
+        _ck(self.dev.L.lssp_amd_ilu_get_schedule(self.h, which, _p(hdr), _p(s["blk"]), _p(s["desc"]), _p(s["rec"]),
+                                                 _p(s["idx"]), _p(s["perm"]), _p(s["pos"])), "ilu_get_schedule")
+        return s
 
     @classmethod
     def bilu(cls, dev: Device, Ap, Aj, Ax, bs: int, level: int = 0):
