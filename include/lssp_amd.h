@@ -407,11 +407,14 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      (lssp_amd_ilut_create_dev): the matrix and the finished factors stay
  *      in HBM, where the sweeps' schedules are built too; factors that
  *      already live in HBM make a handle the same way
- *      (lssp_amd_ilu_from_factors_dev).
+ *      (lssp_amd_ilu_from_factors_dev).  ILUK of any other one-block matrix
+ *      with sorted rows, at any level, is made on the device as well, symbolic
+ *      factorization included; lssp_amd_pc_create_dev is the one call that
+ *      routes to all of them.
  *      What still goes through the host: every other ILU setup
  *      (lssp_amd_ilu_create / lssp_amd_bilu_create take host arrays, as the
- *      reference factors on the host; download the CSR for them: level
- *      >= 2, block-Jacobi, BILUK, general and small 2-D ILUK factors), and the
+ *      reference factors on the host; download the CSR for them:
+ *      block-Jacobi, BILUK, a row without its diagonal), and the
  *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
  *      only when the PATTERN is new: new values on the same pattern stay on the
  *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor /
@@ -667,8 +670,55 @@ int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind,
  * stream has finished. */
 int lssp_amd_ilut_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, double tol, int p, int blk,
                              lssp_amd_ilu **out);
-/* entries a working row of lssp_amd_ilut_create_dev may hold on each side of the diagonal */
+/* entries a working row of lssp_amd_ilut_create_dev (and of lssp_amd_pc_create_dev's
+ * general ILUK route) may hold on each side of the diagonal */
 int lssp_amd_ilut_capacity(void);
+/* One call for every preconditioner handle made from a matrix that lives in
+ * HBM; the arguments mean what they mean in lssp_amd_ilu_create_dev.  Routing:
+ * kind ILUT goes to lssp_amd_ilut_create_dev(ctx, A, tol, p, blk, out), result
+ * returned unchanged.  Kind ILUK (a negative level means the default, 1) first
+ * tries lssp_amd_iluk_create_dev: a complete box keeps its line sweeps, and any
+ * status other than LSSP_AMD_EUNSUPPORTED is returned as is.  What that call
+ * refuses takes the general route, for one block (blk <= 0 or >= n) of a
+ * single-rank A: the ILU(level) of ANY matrix whose rows have strictly ascending
+ * columns inside [0, n) and hold their diagonal -- a thermal-like matrix, an
+ * irregular mesh, a box with holes, level >= 2 of a stencil, an nx == 2 box.
+ * The symbolic factorization (pc-iluk.cxx:22-135, the reference's level rule: a
+ * repeated hit raises a level) runs on the device, one wavefront per row; the
+ * values go through lssp_amd_iluk_refactor's own kernels; the factors are split
+ * and the sweeps' packet schedules built on the device
+ * (lssp_amd_ilu_get_schedule answers origin 1).  No array of A and no factor
+ * array crosses to the host (flag words, two entry counts, Fp[n] and the level
+ * lists' offsets come back); the host copies of the factors are made by their
+ * first reader; A may be destroyed on return.
+ * The general route's handle is bitwise lssp_amd_ilu_create(LSSP_AMD_ILUK,
+ * level)'s of the same matrix in lssp_amd_ilu_apply / _apply_async + _check /
+ * _trisolve / lssp_amd_solve, lssp_amd_ilu_info and _get_factors.
+ * lssp_amd_ilu_sweep_layout answers (0, 0, 0): the route always runs the packet
+ * sweeps (or, for factors beyond the device schedule builder -- a strict row
+ * beyond 24 entries, the packet limits -- the host-built schedules, sync-free
+ * fallback included, from one download of the factors).  In a few shapes
+ * lssp_amd_ilu_create would pick a line route that the box creates refuse (the
+ * one-workgroup 2-D grids, nx == 2, ny < 8 at level 0): there only the layout
+ * answer differs -- every sweep is bitwise the reference's, so no result does.
+ * The handle is made with its refactor plan, flag bytes included (13 B per
+ * entry of the factor pattern + 20 B per row): on the packet sweeps
+ * lssp_amd_iluk_refactor is eligible on it at once and builds nothing.
+ * LSSP_AMD_EUNSUPPORTED from the general route, with *out == NULL, nothing left
+ * allocated, A and ctx usable: block-Jacobi, a distributed A, a row whose
+ * columns are not strictly ascending inside [0, n), a row without its diagonal
+ * (the inserted-diagonal path is not reproduced; lssp_amd_csr_adjust_zero_diag
+ * on the device makes such a matrix eligible), a working row beyond
+ * lssp_amd_ilut_capacity() entries on one side of the diagonal, level > 254
+ * (levels travel as bytes), a factor pattern beyond INT_MAX entries.  NULL
+ * arguments, nrows != ncols, a kind that is neither ILUK nor ILUT:
+ * LSSP_AMD_EINVAL.  A bounded wait of a kernel expired: LSSP_AMD_ETIMEOUT.  A
+ * HIP error part-way: LSSP_AMD_EHIP, everything freed.  LSSP_AMD_SETUP_TIMES=1
+ * prints the phases (check, symbolic, pack, levels, scatter, numeric, split,
+ * then per side the schedule builder's; on the host route download,
+ * schedules).  Returns when the stream has finished. */
+int lssp_amd_pc_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p, int blk,
+                           lssp_amd_ilu **out);
 
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);

@@ -352,7 +352,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 10900; }
+int lssp_amd_version(void) { return 11000; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {
@@ -1273,6 +1273,111 @@ int lssp_amd_ilut_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, double tol,
     if (!c || !A || !out || A->nrows <= 0 || A->nrows != A->ncols) return LSSP_AMD_EINVAL;
     try {
         return ilut_create_dev(c, A, tol, p, blk, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
+// lssp_amd_pc_create_dev's general route: lssp_amd_ilu_create(kind
+// ILUK, level) of any one-block matrix in HBM.  The symbolic ILU(k) factorization
+// runs on the device, a wavefront per row (iluk_symbolic.hip), and leaves the
+// plan lssp_amd_iluk_refactor works on -- F, its flag bytes, diagonal positions
+// and level lists; the values are the refactor's own kernels' (iluk_scatter,
+// k_ilu0_level); F is split into L and U on the device for the device schedule
+// builder (tri_sched.hip), and the split is freed once both schedules stand:
+// a finished TriSched keeps no pointer into the factor arrays it was built from,
+// and the host copies are split from the plan's F by their first reader, so a
+// later refactor leaves no stale factor copy behind.  What the device builder
+// refuses takes the download and ilu_upload, as in ilut_create_dev.
+static int iluk_general_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int level, int blk, lssp_amd_ilu **out)
+{
+    const int n = A->nrows, nnz = A->nnz;
+    if (!(blk <= 0 || blk >= n) || A->dist || A->nhalo > 0) return LSSP_AMD_EUNSUPPORTED;
+    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    LSSP_HIP(hipSetDevice(c->device));
+    const double t_start = wall_time();
+    double t0 = t_start;
+    auto mark = [&](const char *phase) -> int {  // LSSP_AMD_SETUP_TIMES=1: the phases' own durations, the stream drained
+        if (!times) return LSSP_AMD_OK;
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        const double t = wall_time();
+        fprintf(stderr, "lssp_amd pc_create_dev: %-12s %10.6f s\n", phase, t - t0);
+        t0 = t;
+        return LSSP_AMD_OK;
+    };
+    lssp_amd_ilu *M = new lssp_amd_ilu();
+    M->ctx = c;
+    M->n = n;
+    M->c_kind = LSSP_AMD_ILUK;
+    M->c_level = level;
+    M->c_blk = blk;
+    IlutDevFactors S;  // the split: scratch of the schedule builder
+    auto build = [&]() -> int {
+        LSSP_TRY(iluk_symbolic_dev(c, n, nnz, A->Ap, A->Aj, level, &M->rf, mark));
+        RefactorPlan &p = *M->rf;
+        LSSP_TRY(iluk_split_pattern_dev(c, n, p, &S));
+        LSSP_TRY(iluk_plan_levels_dev(c, n, p, S));
+        LSSP_TRY(mark("levels"));
+        LSSP_TRY(iluk_scatter(c, p, n, A->Ap, A->Ax));
+        LSSP_TRY(mark("scatter"));
+        LSSP_TRY(refactor_levels(c, p, n));
+        LSSP_TRY(mark("numeric"));
+        LSSP_TRY(iluk_split_values_dev(c, n, p, S));
+        LSSP_TRY(mark("split"));
+        M->dev_nnzL = S.nnzL;
+        M->dev_nnzU = S.nnzU;
+        M->host_missing = M->host_stale = true;
+        int st = build_trisched_dev(c, n, S.nnzL, S.Lp, S.Lj, S.Lx, false, nullptr, M->lower, mark);
+        if (st == LSSP_AMD_OK)
+            st = build_trisched_dev(c, n, S.nnzU, S.Up, S.Uj, S.Ux, true, M->lower.bp_pos, M->upper, mark);
+        LSSP_HIP(hipStreamSynchronize(c->stream));  // A may be destroyed on return; the split is freed next
+        if (st == LSSP_AMD_EUNSUPPORTED) {
+            // beyond the device builder (a strict row beyond 24 entries, the packet
+            // limits): the host copies from the plan's F and the host schedules,
+            // sync-free fallback included
+            free_trisched(M->lower);
+            free_trisched(M->upper);
+            iluk_split_free(&S);
+            LSSP_TRY(refactor_host_factors(M));
+            LSSP_TRY(mark("download"));
+            setup_mark(nullptr);
+            LSSP_TRY(ilu_upload(c, M));
+            st = mark("schedules");
+        }
+        return st;
+    };
+    int st;
+    try {
+        st = build();
+    } catch (const std::exception &) {
+        st = LSSP_AMD_ENOMEM;
+    }
+    if (st != LSSP_AMD_OK) (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);  // nothing of the split or of the handle is in flight when it is freed
+    iluk_split_free(&S);
+    if (st != LSSP_AMD_OK) {
+        lssp_amd_ilu_destroy(M);
+        return st;
+    }
+    M->setup_seconds = wall_time() - t_start;
+    *out = M;
+    return LSSP_AMD_OK;
+}
+
+int lssp_amd_pc_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int level, double tol, int p, int blk,
+                           lssp_amd_ilu **out)
+{
+    if (out) *out = nullptr;
+    if (!c || !A || !out || A->nrows <= 0 || A->nrows != A->ncols || (kind != LSSP_AMD_ILUK && kind != LSSP_AMD_ILUT))
+        return LSSP_AMD_EINVAL;
+    if (kind == LSSP_AMD_ILUT) return lssp_amd_ilut_create_dev(c, A, tol, p, blk, out);
+    if (level < 0) level = 1;  // the default (pc-iluk.cxx:583-592)
+    // a complete box keeps its line sweeps
+    const int st = lssp_amd_iluk_create_dev(c, A, kind, level, tol, p, blk, out);
+    if (st != LSSP_AMD_EUNSUPPORTED) return st;
+    *out = nullptr;
+    try {
+        return iluk_general_create_dev(c, A, level, blk, out);
     } catch (const std::exception &) {
         return LSSP_AMD_ENOMEM;
     }

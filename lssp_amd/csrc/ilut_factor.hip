@@ -426,6 +426,24 @@ int run_numeric(lssp_amd_ctx *c, const IlutArgs &a0)
 
 int ilut_capacity() { return ILUT_CAP_LARGE; }
 
+// k_ilut_check on its own (lssp_amd_pc_create_dev's general route shares the rule): one flag word read back
+int csr_rows_check_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int *ok)
+{
+    *ok = 0;
+    if (n < 1 || nnz < n) return LSSP_AMD_OK;
+    DevBufs B;
+    int *flag = nullptr;
+    LSSP_HIP(B.get(&flag, 4));
+    LSSP_HIP(hipMemsetAsync(flag, 0, 16, c->stream));
+    k_ilut_check<<<blocks_for(n), 256, 0, c->stream>>>(n, nnz, dAp, dAj, flag);
+    LSSP_HIP(hipGetLastError());
+    int bad = 1;
+    LSSP_HIP(hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    *ok = !bad;
+    return LSSP_AMD_OK;
+}
+
 int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, const double *dAx, double tol,
                     int p, std::vector<int> &Lp, std::vector<int> &Lj, std::vector<double> &Lx,
                     std::vector<int> &Up, std::vector<int> &Uj, std::vector<double> &Ux,

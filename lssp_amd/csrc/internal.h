@@ -661,6 +661,27 @@ int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *
                     int p, std::vector<int> &Lp, std::vector<int> &Lj, std::vector<double> &Lx,
                     std::vector<int> &Up, std::vector<int> &Uj, std::vector<double> &Ux,
                     const std::function<int(const char *)> &mark, IlutDevFactors *keep = nullptr);
+// k_ilut_check's rule on its own (ilut_factor.hip): *ok = Ap starts at 0, ends at nnz and never descends,
+// every row's columns ascend strictly inside [0, n) and hold the diagonal (one flag word read back)
+int csr_rows_check_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int *ok);
+// tri_sched.hip's level pass on its own, for a factor the caller split itself: lev[i] (device) and the count
+int tri_levels_dev(lssp_amd_ctx *c, int n, const int *dTp, const int *dTj, bool upper, int *lev, int *nlevels);
+// lssp_amd_pc_create_dev's general ILUK route (iluk_symbolic.hip, iluk_symbolic_dev.h).
+// iluk_symbolic_dev: the check, then the plan of the level-k pattern of the one-block device CSR -- d_Fp,
+// d_Fj, the flag bytes and the diagonal positions written, d_Fx / d_dinv / d_rows allocated -- made on the
+// device, a wavefront per row (level 0: A's pattern copied).  EUNSUPPORTED: k_ilut_check's rule broken,
+// level > 254, a working row beyond ilut_capacity() entries on a side, Fp[n] beyond INT_MAX; ETIMEOUT: a
+// bounded wait expired.  iluk_split_pattern_dev: Lp / Lj / Up / Uj of F's split (L = strict part + unit
+// diagonal last, U = stored pivot first + strict part) and both entry counts, Lx / Ux allocated;
+// iluk_split_values_dev: Lx / Ux from the factored d_Fx; iluk_split_free: the six arrays.
+// iluk_plan_levels_dev: d_rows and lev_off, the level lists of the numeric DAG (= the L sweep's levels),
+// from the split L by tri_sched.hip's level pass and one stable sort.
+int iluk_symbolic_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *dAj, int level, RefactorPlan **out,
+                      const std::function<int(const char *)> &mark);
+int iluk_split_pattern_dev(lssp_amd_ctx *c, int n, const RefactorPlan &p, IlutDevFactors *S);
+int iluk_split_values_dev(lssp_amd_ctx *c, int n, const RefactorPlan &p, const IlutDevFactors &S);
+void iluk_split_free(IlutDevFactors *S);
+int iluk_plan_levels_dev(lssp_amd_ctx *c, int n, RefactorPlan &p, const IlutDevFactors &S);
 // linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
 // the factored values Fx on the pattern (Fp, Fj); every slot is written
 int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);

@@ -605,4 +605,26 @@ int build_trisched_dev(lssp_amd_ctx *c, int n, int nnz, const int *dTp, const in
     return LSSP_AMD_OK;
 }
 
+// stage 2 on its own, for a factor whose rows the caller made itself (no check pass: every strict column
+// must lie on its side of the diagonal inside [0, n)): lev[i] (device, n words) and the level count
+int tri_levels_dev(lssp_amd_ctx *c, int n, const int *dTp, const int *dTj, bool upper, int *lev, int *nlevels)
+{
+    if (n <= 0 || !dTp || !dTj || !lev || !nlevels) return LSSP_AMD_EINVAL;
+    hipStream_t st = c->stream;
+    DevBufs bufs;
+    int *ctl = nullptr, h_ctl[C_WORDS];
+    LSSP_HIP(bufs.get(&ctl, C_WORDS));
+    LSSP_HIP(hipMemsetAsync(lev, 0xFF, sizeof(int) * (size_t)n, st));  // -1: not written
+    LSSP_HIP(hipMemsetAsync(ctl, 0, sizeof(h_ctl), st));
+    const long nchunks = ((long)n + SCHED_LANES - 1) / SCHED_LANES;
+    const long grid = std::max(1L, std::min((nchunks + 3) / 4, 8L * std::max(c->num_cus, 1)));
+    k_sched_levels<<<(unsigned)grid, 256, 0, st>>>(n, upper ? 1 : 0, dTp, dTj, lev, ctl);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    LSSP_HIP(hipStreamSynchronize(st));
+    if (h_ctl[C_TIMEOUT]) return LSSP_AMD_ETIMEOUT;
+    *nlevels = h_ctl[C_MAXLEV] + 1;
+    return LSSP_AMD_OK;
+}
+
 }  // namespace lssp_amd

@@ -381,6 +381,23 @@ class DILU:
         return _lib.load().lssp_amd_ilut_capacity()
 
     @classmethod
+    def pc_create_dev(cls, dev: Device, A: DMat, kind=ILUK, level=-1, tol=1e-3, p=-1, blk=0):
+        """One call for every handle made from a matrix that lives in HBM (lssp_amd_pc_create_dev).
+        kind=ILUT is ilut_create_dev().  kind=ILUK first tries iluk_create_dev(): a complete box
+        keeps its line sweeps.  Anything that refuses -- a thermal-like matrix, an irregular mesh, a
+        box with holes, level >= 2, nx == 2 -- takes the general route: the symbolic ILU(level)
+        runs on the device, a wavefront per row, the values go through iluk_refactor()'s kernels,
+        and the packet schedules are built on the device (schedule(w)["origin"] == 1;
+        sweep_layout() == (0, 0, 0)); bitwise create(level=level)'s handle, and iluk_refactor()
+        is eligible on it at once.  Rows must be column-sorted and hold their diagonal.
+        Block-Jacobi, an unsorted row, a repeated column, a missing diagonal, a working row beyond
+        ilut_capacity() entries on a side and level > 254 raise LsspError with status 6
+        (unsupported) and leave A as it was: use create() there."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_pc_create_dev(dev.h, A.h, kind, level, tol, p, blk, ctypes.byref(h)), "pc_create_dev")
+        return cls(dev, h)
+
+    @classmethod
     def from_factors(cls, dev: Device, L, U):
         Lp, Lj, Lx = _i32(L[0]), _i32(L[1]), _f64(L[2])
         Up, Uj, Ux = _i32(U[0]), _i32(U[1]), _f64(U[2])
