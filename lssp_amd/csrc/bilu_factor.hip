@@ -248,7 +248,7 @@ int bilu0_factor_gpu(lssp_amd_ctx *c, HostBCSR &T, std::vector<double> &inv)
         fail(hipMemcpyAsync(d_rows, rows.data(), sizeof(int) * nb, hipMemcpyHostToDevice, c->stream));
         fail(hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     }
-    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
+    const bool times = setup_times_on();
     if (times && st == LSSP_AMD_OK) fail(hipStreamSynchronize(c->stream));
     const double t0 = wall_time();
     if (st == LSSP_AMD_OK) {
@@ -389,19 +389,9 @@ int bilu_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M)
 
 int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A)
 {
-    // LSSP_AMD_SETUP_TIMES=1: the phases' own durations (the stream drained after each)
-    static const bool times = getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES"));
-    double t0 = wall_time();
-    auto mark = [&](const char *phase) -> int {
-        if (!times) return LSSP_AMD_OK;
-        LSSP_HIP(hipStreamSynchronize(c->stream));
-        const double t = wall_time();
-        fprintf(stderr, "lssp_amd bilu_refactor: %-22s %10.6f s\n", phase, t - t0);
-        t0 = t;
-        return LSSP_AMD_OK;
-    };
+    PhaseClock clk(c, "bilu_refactor");
     LSSP_TRY(bilu_plan_build(c, M));
-    LSSP_TRY(mark("plan"));
+    LSSP_TRY(clk.mark("plan"));
     BiluPlan &p = *M->brf;
     const int n = M->n, bs = p.bs, bs2 = bs * bs;
     const long nblk = p.nblk;
@@ -418,14 +408,14 @@ int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A
     LSSP_HIP(hipMemcpyAsync(&flag, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));
     if (flag) return LSSP_AMD_EINVAL;  // not the block graph M was created from
-    LSSP_TRY(mark("scatter + graph compare"));
+    LSSP_TRY(clk.mark("scatter + graph compare"));
     // 3. the create's own launches
     bilu0_launch_levels(c, bs, p.lev_off, p.d_rows, p.d_Bp, p.d_Bj, p.d_Bx, p.d_inv, p.d_flag + 1);
     LSSP_HIP(hipGetLastError());
     LSSP_HIP(hipMemcpyAsync(&flag, p.d_flag + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));
     if (flag) return LSSP_AMD_EINVAL;  // singular diagonal block
-    LSSP_TRY(mark("numeric BILU(0)"));
+    LSSP_TRY(clk.mark("numeric BILU(0)"));
     // 4. - 6.: the committed values, the record streams, the inverses
     switch (bs) {
 #define LSSP_BCOMMIT(B)                                                                                        \
@@ -445,13 +435,13 @@ int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A
         return LSSP_AMD_EUNSUPPORTED;
     }
     LSSP_HIP(hipGetLastError());
-    LSSP_TRY(mark("U scaling"));
+    LSSP_TRY(clk.mark("U scaling"));
     LSSP_TRY(launch_pk6_refill(c, M->lower, false, bs, p.nb, p.d_Bp, p.d_Bj, p.d_first, p.d_Fx));
     LSSP_TRY(launch_pk6_refill(c, M->upper, true, bs, p.nb, p.d_Bp, p.d_Bj, p.d_first, p.d_Fx));
     LSSP_HIP(hipMemcpyAsync(M->d_Dinv, p.d_inv, sizeof(double) * (size_t)p.nb * bs2, hipMemcpyDeviceToDevice,
                             c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));
-    LSSP_TRY(mark("packet refill + Dinv"));
+    LSSP_TRY(clk.mark("packet refill + Dinv"));
     return LSSP_AMD_OK;
 }
 

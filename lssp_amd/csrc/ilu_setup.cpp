@@ -856,13 +856,17 @@ int build_trisched(lssp_amd_ctx *c, int n, const std::vector<int> &Tp, const std
     return LSSP_AMD_OK;
 }
 
+void free_sync_free_arrays(TriSched &t)
+{
+    for (void *p : {(void *)t.perm, (void *)t.rp, (void *)t.cols, (void *)t.vals, (void *)t.diag})
+        if (p) (void)hipFree(p);
+    t.perm = t.rp = t.cols = nullptr;
+    t.vals = t.diag = nullptr;
+}
+
 void free_trisched(TriSched &t)
 {
-    if (t.perm) (void)hipFree(t.perm);
-    if (t.rp) (void)hipFree(t.rp);
-    if (t.cols) (void)hipFree(t.cols);
-    if (t.vals) (void)hipFree(t.vals);
-    if (t.diag) (void)hipFree(t.diag);
+    free_sync_free_arrays(t);
     for (void *p : {(void *)t.bp_perm, (void *)t.bp_pos, (void *)t.pk6_blk, (void *)t.pk6_desc, (void *)t.pk6_idx, (void *)t.pk6_rec,
                     (void *)t.pk6_claim})
         if (p) (void)hipFree(p);

@@ -358,28 +358,6 @@ __global__ __launch_bounds__(256) void k_iluk_split(int n, const int *__restrict
     }
 }
 
-struct DevBufs {  // the call's temporaries; freed on every path
-    std::vector<void *> all;
-    template <typename T>
-    hipError_t get(T **p, size_t count)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, sizeof(T) * std::max<size_t>(count, 1));
-        if (e == hipSuccess) all.push_back(q);
-        *p = (T *)q;
-        return e;
-    }
-    void drop(void *q)
-    {
-        all.erase(std::remove(all.begin(), all.end(), q), all.end());
-        (void)hipFree(q);
-    }
-    ~DevBufs()
-    {
-        for (void *q : all) (void)hipFree(q);
-    }
-};
-
 unsigned blocks_for(long long items) { return (unsigned)std::max<long long>(1, std::min<long long>((items + 255) / 256, 16384)); }
 
 int scan_excl(lssp_amd_ctx *c, DevBufs &B, const int *in, int *out, size_t cnt)
@@ -403,7 +381,7 @@ int run_symbolic(lssp_amd_ctx *c, const IlukArgs &a0)
     a.chunk = (int)std::min<long>(std::max<long>(a.n / (64 * cus), ILUK_CHUNK_MIN), ILUK_CHUNK_MAX);
     const long nchunks = ((long)a.n + a.chunk - 1) / a.chunk;
     const long grid = std::max(1L, std::min(nchunks, 32 * cus));
-    if (getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES")))
+    if (setup_times_on())
         fprintf(stderr, "lssp_amd pc_create_dev: capacity %d, grid %ld, chunks of %d rows\n", CAP, grid, a.chunk);
     LSSP_HIP(hipMemsetAsync(a.ucnt, 0xFF, sizeof(int) * (size_t)a.n, c->stream));  // -1: not finished
     LSSP_HIP(hipMemsetAsync(a.ctl, 0, 16, c->stream));

@@ -383,23 +383,6 @@ __global__ __launch_bounds__(256) void k_ilut_pack(IlutArgs a, int len0, const i
     }
 }
 
-struct DevBufs {  // everything the call allocates; freed on every path
-    std::vector<void *> all;
-    template <typename T>
-    hipError_t get(T **p, size_t count)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, sizeof(T) * std::max<size_t>(count, 1));
-        if (e == hipSuccess) all.push_back(q);
-        *p = (T *)q;
-        return e;
-    }
-    ~DevBufs()
-    {
-        for (void *q : all) (void)hipFree(q);
-    }
-};
-
 unsigned blocks_for(long long items) { return (unsigned)std::min<long long>((items + 255) / 256, 65536); }
 
 template <int CAP>
@@ -413,7 +396,7 @@ int run_numeric(lssp_amd_ctx *c, const IlutArgs &a0)
     a.chunk = (int)std::min<long>(std::max<long>(a.n / (64 * cus), ILUT_CHUNK_MIN), ILUT_CHUNK_MAX);
     const long nchunks = ((long)a.n + a.chunk - 1) / a.chunk;
     const long grid = std::max(1L, std::min(nchunks, 32 * cus));
-    if (getenv("LSSP_AMD_SETUP_TIMES") && atoi(getenv("LSSP_AMD_SETUP_TIMES")))
+    if (setup_times_on())
         fprintf(stderr, "lssp_amd ilut_create_dev: capacity %d, grid %ld, chunks of %d rows\n", CAP, grid, a.chunk);
     LSSP_TRY(launch_fill(c, a.diag, a.n, TRI_SENTINEL));
     LSSP_HIP(hipMemsetAsync(a.ctl, 0, 16, c->stream));
@@ -484,10 +467,8 @@ int ilut_factor_dev(lssp_amd_ctx *c, int n, int nnz, const int *dAp, const int *
         if ((long long)n * (a.keep + 1) + len0 > (long long)INT_MAX) return LSSP_AMD_EUNSUPPORTED;
         const size_t st = (size_t)ilut_stage_off(n, a.keep);
         if (sj) {  // the retry's staging areas replace the first try's
-            (void)hipFree(sj);
-            (void)hipFree(sx);
-            B.all.erase(std::remove_if(B.all.begin(), B.all.end(), [&](void *q) { return q == sj || q == sx; }),
-                        B.all.end());
+            B.drop(sj);
+            B.drop(sx);
         }
         LSSP_HIP(B.get(&sj, 2 * st));
         LSSP_HIP(B.get(&sx, 2 * st));

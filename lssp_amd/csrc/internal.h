@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -479,8 +480,29 @@ int ensure_part(lssp_amd_ctx *c, long C);
 // with lssp_amd_set_print, else to stdout (flushed, as lssp_printf does)
 int lprint(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 double wall_time();  // seconds, lssp_get_time() (utils.cxx:40-46)
-// setup phase timings to stderr when LSSP_AMD_SETUP_TIMES=1 (tuning aid)
+// LSSP_AMD_SETUP_TIMES=1 (tuning aid): the setup phases' times go to stderr.  The
+// variable's one reader; read at the first call and kept
+bool setup_times_on();
+// the host setup's phases: "lssp_amd setup: <phase> <seconds> s" (setup_times_on())
 void setup_mark(const char *phase);
+// The clock of one create or refactor.  mark(phase) prints "lssp_amd <tag>: <phase>
+// <seconds> s", the time since the last mark, when setup_times_on() -- after
+// draining c's stream when drain is set, so that a phase's time is its own;
+// without the variable it does nothing.  total(): the call's setup_seconds.
+// Converts to the mark callback the device builders take.
+struct PhaseClock {
+    lssp_amd_ctx *c;
+    const char *tag;
+    bool drain;
+    double t_start, t0;
+    PhaseClock(lssp_amd_ctx *c, const char *tag, bool drain = true);
+    int mark(const char *phase);
+    double total() const;
+    operator std::function<int(const char *)>()
+    {
+        return [this](const char *phase) { return mark(phase); };
+    }
+};
 // a sub-phase's own duration (LSSP_AMD_SETUP_TIMES; thread-safe: no shared clock)
 struct SetupTimer {
     double t0;
@@ -492,6 +514,31 @@ struct SetupTimer {
 int host_threads();  // worker threads for host setup: <= 16, <= OMP_NUM_THREADS
 // [0, n) cut into at most 16 contiguous ranges of >= grain items, one thread each
 void parallel_for(long n, const std::function<void(long, long)> &f, long grain = 4096);
+// a host CSR's shape: Ap from 0 to nnz and never descending, columns inside [0, ncols); else EINVAL
+int check_csr(int nrows, int ncols, int nnz, const int *Ap, const int *Aj);
+
+// the hipMallocs of one call (the device builders' temporaries): freed on every path out of it
+struct DevBufs {
+    std::vector<void *> all;
+    template <typename T>
+    hipError_t get(T **p, size_t count)
+    {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, sizeof(T) * std::max<size_t>(count, 1));
+        if (e == hipSuccess) all.push_back(q);
+        *p = (T *)q;
+        return e;
+    }
+    void drop(void *q)
+    {
+        all.erase(std::remove(all.begin(), all.end(), q), all.end());
+        (void)hipFree(q);
+    }
+    ~DevBufs()
+    {
+        for (void *q : all) (void)hipFree(q);
+    }
+};
 
 // ILU setup (ilu_setup.cpp), exact restatement of pc-iluk.cxx / pc-ilut.cxx
 struct HostCSR {
@@ -530,7 +577,7 @@ void bilu_expand(const HostBCSR &T, const std::vector<double> &inv, HostCSR &L, 
 // launches): rows[off[l] .. off[l + 1]) is level l, ascending inside a level
 void bilu_levels(int nb, const std::vector<int> &Bp, const std::vector<int> &Bj, std::vector<int> &off,
                  std::vector<int> &rows);
-// lssp_amd_bilu_refactor (capi.cpp).  bilu_factor.hip: the plan from the kept
+// lssp_amd_bilu_refactor (ilu_handle.cpp).  bilu_factor.hip: the plan from the kept
 // block pattern; the device steps (scatter, graph compare, k_bilu0_level, U
 // scaling, packet refill, d_Dinv), EINVAL with the handle's live state untouched
 // when A breaks the pattern rule or a diagonal block is singular; Lx / Ux / Dinv
@@ -597,7 +644,7 @@ int launch_linefill_apply_tail(lssp_amd_ctx *c, const LineILU &li, double *x, co
                                long *tail_waves);
 int launch_linefill_sweep(lssp_amd_ctx *c, const LineILU &li, int which, double *x, const double *rhs);
 void free_line_sweep(LineILU &li);
-// lssp_amd_ilu_refactor (capi.cpp).  ilu_factor.hip: the plan from the host
+// lssp_amd_ilu_refactor (ilu_handle.cpp).  ilu_factor.hip: the plan from the host
 // copies of the factor pattern; *same = A's device pattern equals it; the
 // numeric ILU(0) of Ax (device, plan order) into d_Fx; Lx / Ux from d_Fx.
 int refactor_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M, bool with_flags = false);
@@ -605,7 +652,7 @@ void refactor_plan_free(RefactorPlan *p);
 int refactor_same_pattern(lssp_amd_ctx *c, const RefactorPlan &p, int n, const int *dAp, const int *dAj, int *same);
 int refactor_numeric(lssp_amd_ctx *c, RefactorPlan &p, int n, const double *dAx);
 int refactor_host_factors(lssp_amd_ilu *M);
-// lssp_amd_iluk_refactor's own routes (capi.cpp; ilu_factor.hip, DESIGN.md
+// lssp_amd_iluk_refactor's own routes (ilu_handle.cpp; ilu_factor.hip, DESIGN.md
 // 3.3c), on a plan built with the flag bytes.  iluk_match: *ok = A's device
 // pattern obeys the pattern rule (nothing written).  iluk_scatter_numeric: A's
 // values onto F (fill +0.0, inserted diagonals ZERO_DIAG_TOL), then
@@ -709,6 +756,9 @@ bool line_gather_ew_ok(const LineILU &li, long n);
 int launch_line_gather_ew(lssp_amd_ctx *c, const LineILU &li, int op, const double *x, const double *y, double *out,
                           const double *scal);
 void free_trisched(TriSched &t);
+// the sync-free sweep's arrays of t alone (perm, rp, cols, vals, diag), the pointers cleared: a refactor drops
+// them, the next single sweep builds them again (ensure_sync_free)
+void free_sync_free_arrays(TriSched &t);
 
 // reductions with the context's mode; result left in d_sums / scal per Fin
 int finish_reduce(lssp_amd_ctx *c, long n, int nslot, const double *const *a,

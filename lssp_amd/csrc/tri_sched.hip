@@ -352,28 +352,6 @@ __global__ __launch_bounds__(SCHED_LANES) void k_sched_fill(int npk, int upper, 
     }
 }
 
-struct DevBufs {  // the call's temporaries; freed on every path
-    std::vector<void *> all;
-    template <typename T>
-    hipError_t get(T **p, size_t count)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, sizeof(T) * std::max<size_t>(count, 1));
-        if (e == hipSuccess) all.push_back(q);
-        *p = (T *)q;
-        return e;
-    }
-    void drop(void *q)
-    {
-        all.erase(std::remove(all.begin(), all.end(), q), all.end());
-        (void)hipFree(q);
-    }
-    ~DevBufs()
-    {
-        for (void *q : all) (void)hipFree(q);
-    }
-};
-
 unsigned blocks_for(long long items) { return (unsigned)std::max<long long>(1, std::min<long long>((items + 255) / 256, 65536)); }
 
 template <typename T>
