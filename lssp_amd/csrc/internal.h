@@ -29,7 +29,7 @@ constexpr uint64_t TRI_SENTINEL = 0xFFF7DEADBEEFCAFEull;
 // scalar slots of the Krylov drivers (device memory, ctx->d_scal)
 enum Scal {
     S_RHO0 = 0, S_RHO1, S_ALPHA, S_BETA, S_OMEGA, S_RES, S_SNORM, S_BREAK, S_BNORM, S_TMP,
-    S_DONE, S_TOL, S_NIT,  // batched iterations (solvers.cpp cg): stop flag, tolerance, iterations run
+    S_DONE, S_TOL, S_NIT,  // batched iterations (solvers.cpp Run::batches: bicgstab, cg): stop flag, tolerance, iterations run
     S_SUM0 = 16,   // raw reduced sums of the last reduction
     S_H = 32,      // GMRES Hessenberg column (up to NSCAL - 32 entries); batched residual history ring
     S_HB = 64,     // ... of S_HB entries: iteration k's residual at S_H + k % S_HB (two batches in flight)
@@ -82,7 +82,7 @@ struct lssp_amd_ctx {
     int *d_err = nullptr;      // error word (trisolve timeouts)
     // batched iterations: the stream copies each batch's scalars and error word
     // into snapshot k (pinned) and records ev_snap[k], so the host reads batch
-    // j while batch j + 1 runs (solvers.cpp Pipe)
+    // j while batch j + 1 runs (solvers.cpp Run::batches)
     double *h_snap = nullptr;  // [2][S_H + S_HB]
     int *h_snap_err = nullptr; // [2]
     hipEvent_t ev_snap[2] = {nullptr, nullptr};

@@ -98,14 +98,7 @@ struct Run {
     }
     int pc(double *x, const double *rhs)
     {
-        if (!M) {
-            Ew e;
-            e.kind = K_COPY;
-            e.n = n;
-            e.x = rhs;
-            e.out0 = x;
-            return launch_ew(c, e);
-        }
+        if (!M) return copy(rhs, x);
         if (gpc) return pc_global(x, rhs);
         return launch_ilu_apply(c, M, x, rhs);
     }
@@ -121,16 +114,10 @@ struct Run {
             g_x = vec(ng);
             if (!g_send || !g_rhs || !g_x) return LSSP_AMD_ENOMEM;
         }
-        Ew e;
-        e.kind = K_COPY;
-        e.x = rhs;
-        e.out0 = g_send;
-        LSSP_TRY(ew(e));
+        LSSP_TRY(copy(rhs, g_send));
         LSSP_TRY(comm_allgather(c, g_send, g_rhs, (long)sizeof(double) * blk));
         LSSP_TRY(launch_ilu_apply(c, M, g_x, g_rhs));
-        e.x = g_x + A->row0;
-        e.out0 = x;
-        return ew(e);
+        return copy(g_x + A->row0, x);
     }
     // x = M^-1 rhs, then z = op(A x) (+ fused dots): one rank with a line-swept
     // ILU(0) runs the product in the U sweep's tail, as planes of x become
@@ -155,14 +142,16 @@ struct Run {
         int e = 0;
         LSSP_HIP(hipMemcpyAsync(&e, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         LSSP_HIP(hipStreamSynchronize(c->stream));
-        if (e) {
-            LSSP_HIP(hipMemset(c->d_err, 0, sizeof(int)));
-            // a line sweep that gave up mid-way leaves hand-off entries written
-            if (M && M->line.ntiles) LSSP_TRY(line_rearm(c, const_cast<lssp_amd_ilu *>(M)->line));
-            LSSP_HIP(hipStreamSynchronize(c->stream));
-            return LSSP_AMD_ETIMEOUT;
-        }
-        return LSSP_AMD_OK;
+        return e ? recover() : LSSP_AMD_OK;
+    }
+    // the error word was set: a bounded wait on the device expired.  Clear it and put
+    // the hand-off entries back that a line sweep which gave up mid-way left written
+    int recover()
+    {
+        LSSP_HIP(hipMemset(c->d_err, 0, sizeof(int)));
+        if (M && M->line.ntiles) LSSP_TRY(line_rearm(c, const_cast<lssp_amd_ilu *>(M)->line));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        return LSSP_AMD_ETIMEOUT;
     }
     // batched iterations, two batches in flight: the stream copies the scalar
     // slots (0 .. S_H + S_HB: the stop flag, the iteration count and the residual
@@ -184,10 +173,7 @@ struct Run {
         memcpy(c->h_scal, c->h_snap + k * (S_H + S_HB), sizeof(double) * (S_H + S_HB));
         if (c->h_snap_err[k]) {
             LSSP_HIP(hipStreamSynchronize(c->stream));  // the batch queued after it runs out first
-            LSSP_HIP(hipMemset(c->d_err, 0, sizeof(int)));
-            if (M && M->line.ntiles) LSSP_TRY(line_rearm(c, const_cast<lssp_amd_ilu *>(M)->line));
-            LSSP_HIP(hipStreamSynchronize(c->stream));
-            return LSSP_AMD_ETIMEOUT;
+            return recover();
         }
         return LSSP_AMD_OK;
     }
@@ -199,6 +185,54 @@ struct Run {
         c->h_scal[S_NIT] = 0.0;
         LSSP_HIP(hipMemcpyAsync(c->d_scal + S_DONE, c->h_scal + S_DONE, 3 * sizeof(double), hipMemcpyHostToDevice,
                                 c->stream));
+        return LSSP_AMD_OK;
+    }
+    // one queued batch: its first iteration and its length; per iteration the trace
+    // length after it and, for BiCGSTAB, the trace position before its ||s||
+    struct Batch {
+        int it0 = 0, nb = 0;
+        long tl_after[S_HB / 2], pos_s[S_HB / 2];
+    };
+    // iteration it0 + q's residual, from the snapshot of the history ring
+    double hist(const Batch &B, int q) const { return h(S_H + (B.it0 + q) % S_HB); }
+    // The pump: up to maxit iterations in batches of BATCH.  enqueue(k, j, B) queues
+    // iteration k, the j-th of batch B (B.nb is set); read(B, ran, done, stop) gets a
+    // batch whose snapshot has arrived -- ran: the iterations of it that ran (the one
+    // that stopped included), done: its S_DONE -- and sets stop to end the run.
+    template <int BATCH, class Enqueue, class Read>
+    int batches(double tol, int maxit, Enqueue enqueue, Read read)
+    {
+        static_assert(2 * BATCH <= S_HB, "two batches in the residual history ring");
+        Batch bq[2];
+        int queued = 0, nq = 0, nr = 0;  // iterations queued, batches queued, batches read
+        auto push = [&]() -> int {
+            Batch &B = bq[nq & 1];
+            B.it0 = queued;
+            B.nb = std::min(BATCH, maxit - queued);
+            c->guard = c->d_scal + S_DONE;
+            int st = LSSP_AMD_OK;
+            for (int j = 0; j < B.nb && st == LSSP_AMD_OK; j++) {
+                st = enqueue(queued + j, j, B);
+                B.tl_after[j] = tl;
+            }
+            c->guard = nullptr;
+            LSSP_TRY(st);
+            LSSP_TRY(snap_issue(nq & 1));
+            queued += B.nb;
+            nq++;
+            return LSSP_AMD_OK;
+        };
+        LSSP_TRY(batch_begin(tol));
+        LSSP_TRY(push());
+        for (;;) {
+            if (queued < maxit) LSSP_TRY(push());  // runs while the batch before it is read
+            const Batch &B = bq[nr & 1];
+            LSSP_TRY(snap_wait(nr & 1));
+            nr++;
+            bool stop = false;
+            LSSP_TRY(read(B, std::max(1, std::min(B.nb, (int)h(S_NIT) - B.it0)), h(S_DONE), stop));
+            if (stop || nr == nq) break;  // nr == nq: maxit
+        }
         return LSSP_AMD_OK;
     }
     double h(int i) const { return c->h_scal[i]; }
@@ -213,6 +247,14 @@ struct Run {
         e.scal = c->d_scal;
         if (!tree) e.nred = 0;
         return launch_ew(c, e);
+    }
+    int copy(const double *src, double *dst)  // lssp_vec_copy
+    {
+        Ew e;
+        e.kind = K_COPY;
+        e.x = src;
+        e.out0 = dst;
+        return ew(e);
     }
     int fin1(const double *a, const double *b, const Fin &f)
     {
@@ -238,6 +280,40 @@ void defaults(const lssp_amd_solve_params &P, double &tol_rel, double &tol_abs, 
     maxit = P.maxit <= 0 ? DEF_MAXIT : P.maxit;
 }
 
+// the stop scale max(tol_rel ||r0||, tol_abs, tol_rb ||b||); tol_rb comes scaled by ||b||
+double stop_scale(double tol_rel, double tol_abs, double tol_rb, double r0)
+{
+    double tol = r0 * tol_rel;
+    if (tol < tol_abs) tol = tol_abs;
+    if (tol < tol_rb) tol = tol_rb;
+    return tol;
+}
+
+// the verb >= 2 lines every driver that prints them has in common, and the verb >= 1
+// line of an iteration with the residual over ||b||
+void print_header(const Run &R, const lssp_amd_solve_params &P, const char *name, int maxit, double tol_abs,
+                  double tol_rel, double tol_rb)
+{
+    if (P.verb < 2 || R.rank != 0) return;
+    lprint("%s: maximal iteration: %d\n", name, maxit);
+    lprint("%s: tolerance abs: %g\n", name, tol_abs);
+    lprint("%s: tolerance rel: %g\n", name, tol_rel);
+    lprint("%s: tolerance rbn: %g\n", name, tol_rb);
+}
+void print_footer(const Run &R, const lssp_amd_solve_params &P, const char *name, int nits, double t_start)
+{
+    if (P.verb < 2 || R.rank != 0) return;
+    lprint("%s: total iteration: %d\n", name, nits);
+    lprint("%s: total time: %g\n", name, wall_time() - t_start);
+}
+void print_itr(const Run &R, const lssp_amd_solve_params &P, const char *name, int k, double res, double err_rel,
+               double b_norm)
+{
+    if (P.verb >= 1 && R.rank == 0)
+        lprint("%s: itr: %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", name, k, res,
+               (err_rel == 0 ? 0 : res / err_rel), (b_norm == 0 ? 0 : res / b_norm));
+}
+
 // ---------------------------------------------------------------------------
 // BiCGSTAB, right preconditioned (solver-bicgstab.cxx:10-175)
 // ---------------------------------------------------------------------------
@@ -248,24 +324,13 @@ int bicgstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
     double tol_rel, tol_abs, tol_rb = P.tol_rb, tol;
     int maxit, it;
     defaults(P, tol_rel, tol_abs, maxit);
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("bicgstab: maximal iteration: %d\n", maxit);
-        lprint("bicgstab: tolerance abs: %g\n", tol_abs);
-        lprint("bicgstab: tolerance rel: %g\n", tol_rel);
-        lprint("bicgstab: tolerance rbn: %g\n", tol_rb);
-    }
+    print_header(R, P, "bicgstab", maxit, tol_abs, tol_rel, tol_rb);
     double *r = R.vec(), *rh = R.vec(), *p = R.vec(), *ph = R.vec();
     double *s = R.vec(), *sh = R.vec(), *t = R.vec(), *v = R.vec();
     if (!r || !rh || !p || !ph || !s || !sh || !t || !v) return LSSP_AMD_ENOMEM;
 
     LSSP_TRY(R.spmv(EPI_AXPBY, -1, x, 1, b, r));  // :67
-    {
-        Ew e;
-        e.kind = K_COPY;
-        e.x = r;
-        e.out0 = rh;
-        LSSP_TRY(R.ew(e));  // :68-71 (the sh/ph zero fill is dead work)
-    }
+    LSSP_TRY(R.copy(r, rh));                      // :68-71 (the sh/ph zero fill is dead work)
     LSSP_TRY(R.dot1(b, b, R.fin(FIN_NORM, 1, R.T(), -1, S_BNORM)));  // :73
     LSSP_TRY(R.dot1(r, r, R.fin(FIN_NORM, 1, R.T(), -1, S_RES)));    // :76
     LSSP_TRY(R.sync(0, 16));
@@ -278,9 +343,7 @@ int bicgstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
         *res_out = res;
         return LSSP_AMD_OK;
     }
-    tol = res * tol_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
+    tol = stop_scale(tol_rel, tol_abs, tol_rb, res);
 
     LSSP_TRY(R.dot1(r, rh, R.fin(FIN_BICG_RHO, 1, R.T())));  // :87 (first iteration)
     LSSP_TRY(R.sync(0, 16));
@@ -299,10 +362,7 @@ int bicgstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
     auto enqueue = [&](int k, int fin_res, long *pos_s) -> int {
         Ew e;
         if (k == 0) {
-            e.kind = K_COPY;  // :96
-            e.x = r;
-            e.out0 = p;
-            LSSP_TRY(R.ew(e));
+            LSSP_TRY(R.copy(r, p));  // :96
         } else if (gew) {
             LSSP_TRY(launch_line_gather_ew(R.c, R.M->line, GEW_BICG_P, r, v, p, R.c->d_scal));  // :99-102
         } else {
@@ -378,11 +438,7 @@ int bicgstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
         res = R.h(S_RES);
         return LSSP_AMD_OK;
     };
-    auto itr_line = [&](int k, double rk) {
-        if (P.verb >= 1 && R.rank == 0)
-            lprint("bicgstab: itr: %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", k, rk,
-                   (err_rel == 0 ? 0 : rk / err_rel), (b_norm == 0 ? 0 : rk / b_norm));
-    };
+    auto itr_line = [&](int k, double rk) { print_itr(R, P, "bicgstab", k, rk, err_rel, b_norm); };
     const bool batched = !R.M || R.M->line.ntiles > 0;
     if (batched && rho1 == 0) {  // :89-92 at the first iteration
         if (R.rank == 0) lprint("bicgstab: method failed.!\n");
@@ -393,69 +449,40 @@ int bicgstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
         // breakdown :117, res <= tol :149, rho1 == 0 :89 of the next); the
         // launches past the stop return at once (ctx guard), and the host reads a
         // batch's residuals from its snapshot while the next batch runs
-        // (Run::snap_issue).  Same kernels, same arithmetic.
+        // (Run::batches).  Same kernels, same arithmetic.
         constexpr int BATCH = 8;
-        static_assert(2 * BATCH <= S_HB, "two batches in the residual history ring");
-        lssp_amd_ctx *c = R.c;
-        struct Batch {
-            int it0 = 0, nb = 0;
-            long tl_after[BATCH], pos_s[BATCH];
-        } bq[2];
-        int queued = 0, nq = 0, nr = 0;  // iterations queued, batches queued, batches read
-        auto push = [&]() -> int {
-            Batch &B = bq[nq & 1];
-            B.it0 = queued;
-            B.nb = std::min(BATCH, maxit - queued);
-            c->guard = c->d_scal + S_DONE;
-            int st = LSSP_AMD_OK;
-            for (int j = 0; j < B.nb && st == LSSP_AMD_OK; j++) {
-                st = enqueue(queued + j, FIN_BICG_RES_RHO_B, &B.pos_s[j]);
-                B.tl_after[j] = R.tl;
-            }
-            c->guard = nullptr;
-            LSSP_TRY(st);
-            LSSP_TRY(R.snap_issue(nq & 1));
-            queued += B.nb;
-            nq++;
-            return LSSP_AMD_OK;
-        };
         it = 0;
-        LSSP_TRY(R.batch_begin(tol));
-        LSSP_TRY(push());
-        for (;;) {
-            if (queued < maxit) LSSP_TRY(push());  // runs while the batch before it is read
-            const Batch &B = bq[nr & 1];
-            LSSP_TRY(R.snap_wait(nr & 1));
-            nr++;
-            auto hist = [&](int q) { return R.h(S_H + (B.it0 + q) % S_HB); };
-            const int ran = std::max(1, std::min(B.nb, (int)R.h(S_NIT) - B.it0));
-            const int code = (int)R.h(S_DONE);
-            for (int q = 0; q < ran - (code == 2 ? 1 : 0); q++) itr_line(it + q, hist(q));
-            res = hist(ran - 1);
+        auto queue = [&](int k, int j, Run::Batch &B) { return enqueue(k, FIN_BICG_RES_RHO_B, &B.pos_s[j]); };
+        auto read = [&](const Run::Batch &B, int ran, double done, bool &stop) -> int {
+            const int code = (int)done;
+            for (int q = 0; q < ran - (code == 2 ? 1 : 0); q++) itr_line(it + q, R.hist(B, q));
+            res = R.hist(B, ran - 1);
             pending_rho = true;
+            stop = true;
             if (code == 2) {  // breakdown in iteration it + ran - 1
                 it += ran - 1;
                 pending_rho = false;
-                LSSP_TRY(breakdown(B.pos_s[ran - 1]));
-                break;
+                return breakdown(B.pos_s[ran - 1]);
             } else if (code == 1) {  // converged
                 R.tl = B.tl_after[ran - 1];
                 it += ran - 1;
-                break;
+                return LSSP_AMD_OK;
             } else if (code == 3) {  // the next iteration's rho1 == 0
                 R.tl = B.tl_after[ran - 1];
                 it += ran;
                 pending_rho = false;
                 if (it < maxit) {
                     if (R.rank == 0) lprint("bicgstab: method failed.!\n");
-                    break;
+                    return LSSP_AMD_OK;
                 }
                 pending_rho = true;
             } else {
                 it += B.nb;
             }
-            if (nr == nq) break;  // maxit
-        }
+            stop = false;
+            return LSSP_AMD_OK;
+        };
+        LSSP_TRY(R.batches<BATCH>(tol, maxit, queue, read));
     } else {
         for (it = 0; it < maxit; it++) {
             pending_rho = false;
@@ -479,10 +506,7 @@ int bicgstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
     }
     if (pending_rho) R.tl--;  // the fused next-iteration rho1 is not part of the reference's run
     if (it < maxit) it += 1;  // :152
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("bicgstab: total iteration: %d\n", it);
-        lprint("bicgstab: total time: %g\n", wall_time() - t_start);
-    }
+    print_footer(R, P, "bicgstab", it, t_start);
     *nits = it;
     *res_out = res;
     return LSSP_AMD_OK;
@@ -497,12 +521,7 @@ int cg(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *
     double tol_rel, tol_abs, tol_rb = P.tol_rb, tol;
     int maxit, it;
     defaults(P, tol_rel, tol_abs, maxit);
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("cg: maximal iteration: %d\n", maxit);
-        lprint("cg: tolerance abs: %g\n", tol_abs);
-        lprint("cg: tolerance rel: %g\n", tol_rel);
-        lprint("cg: tolerance rbn: %g\n", tol_rb);
-    }
+    print_header(R, P, "cg", maxit, tol_abs, tol_rel, tol_rb);
     double *r = R.vec(), *p = R.vec(), *q = R.vec();
     double *z = R.M ? R.vec() : r;  // PC_NON copies r into z (pc.cxx:67-70): alias instead
     if (!r || !p || !q || !z) return LSSP_AMD_ENOMEM;
@@ -520,145 +539,57 @@ int cg(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *
         return LSSP_AMD_OK;
     }
     const double err_rel = res;
-    tol = tol_rel * err_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
-    bool pending_rho = false;
+    tol = stop_scale(tol_rel, tol_abs, tol_rb, err_rel);
+    bool pending_rho = false;  // a fused next-iteration rho1 sits in the trace
 
-    if (!R.M) {
-        // PC_NON: iterations are queued in batches and the stop
-        // test :109 runs on the device (FIN_CG_RES_RHO_B); the launches of the
-        // iterations after the one that converged return at once (ctx guard),
-        // and the host reads a batch's residuals from its snapshot while the
-        // next batch runs (Run::snap_issue).  Same kernels, same arithmetic.
+    // PC_NON: iterations are queued in batches and the stop test :109 runs on
+    // the device (FIN_CG_RES_RHO_B, which also forms the next :80 as z == r); the
+    // launches of the iterations after the one that converged return at once
+    // (ctx guard), and the host reads a batch's residuals from its snapshot
+    // while the next batch runs (Run::batches).  Same kernels, same arithmetic.
+    const bool batched = !R.M;
 #ifndef CG_BATCH
 #define CG_BATCH 32  // config 5: 32 against 16 / 8 per batch 21.54-21.84 K / 21.34-21.44 K / 20.98-21.09 K it/s (r06u)
 #endif
-        constexpr int BATCH = CG_BATCH;  // iterations per batch (A/B: -DCG_BATCH)
-        static_assert(2 * BATCH <= S_HB, "two batches in the residual history ring");
-        lssp_amd_ctx *c = R.c;
-        const bool fuse_l2 = R.tree && c->nranks == 1 && R.n > 0;
-        struct Batch {
-            int it0 = 0, nb = 0;
-            long tl_after[BATCH];
-        } bq[2];
-        int queued = 0, nq = 0, nr = 0;  // iterations queued, batches queued, batches read
-        auto push = [&]() -> int {
-            Batch &B = bq[nq & 1];
-            B.it0 = queued;
-            B.nb = std::min(BATCH, maxit - queued);
-            c->guard = c->d_scal + S_DONE;
-            int st = LSSP_AMD_OK;
-            // one rank, tree reductions: each reduction's level 2 runs inside
-            // the vector update that consumes it (k_cg_fused): q.p (partial
-            // row 0, from the product) in the x/r update, r.r (row 1) in the
-            // next iteration's p update; the batch's last r.r on its own.
-            // Stamps are global iteration counts (FIN_CG_RES_RHO_B's S_DONE)
-            Fin held;
-            bool have_held = false;
-            for (int j = 0; j < B.nb && st == LSSP_AMD_OK; j++) {
-                const int k = queued + j;
-                Ew e;
-                if (k == 0) {
-                    st = R.dot1(r, r, R.fin(FIN_CG_RHO, 1, R.T()));  // :80 (z == r)
-                    e.kind = K_COPY;                                  // :83-86
-                } else {
-                    e.kind = K_CG_P;  // :88-92
-                }
-                e.x = z;
-                e.out0 = p;
-                if (st == LSSP_AMD_OK) {
-                    // with the x update of the previous x/r pass (CGF_R): its stop test is stamped k
-                    if (have_held) st = launch_cg_fused(c, CGF_PX, R.n, x, p, nullptr, z, nullptr, 1, 1, held, k);
-                    else st = R.ew(e);
-                }
-                have_held = false;
-                if (st == LSSP_AMD_OK) st = R.spmv(EPI_MXY, 1, p, 0, nullptr, q, 1, p);  // :95
-                const Fin fa = R.fin(FIN_CG_ALPHA, 1, R.T());                            // :96-99
-                if (fuse_l2) {
-                    // r only: x += alpha p (:102) rides with the next p pass, or the batch's CGF_X
-                    if (st == LSSP_AMD_OK) st = launch_cg_fused(c, CGF_R, R.n, x, p, r, nullptr, q, 0, 1, fa);
-                } else {
-                    if (st == LSSP_AMD_OK) st = R.fin1(q, p, fa);
-                    e = Ew();
-                    e.kind = K_CG_XR;  // :101-104
-                    e.out0 = x;
-                    e.x = p;
-                    e.out1 = r;
-                    e.y = q;
-                    e.nred = 1;
-                    e.r0a = r;
-                    e.r0b = r;
-                    if (st == LSSP_AMD_OK) st = R.ew(e);
-                }
-                int t0 = R.T(), t1 = R.T();
-                const Fin fr = R.fin(FIN_CG_RES_RHO_B, 1, t0, t1);  // :106-109, next :80
-                if (fuse_l2 && j + 1 < B.nb) {
-                    held = fr;
-                    have_held = true;
-                } else if (fuse_l2) {
-                    if (st == LSSP_AMD_OK) st = launch_reduce_tree(c, num_chunks(R.n), 1, fr, 1);
-                    if (st == LSSP_AMD_OK)
-                        st = launch_cg_fused(c, CGF_X, R.n, x, p, nullptr, nullptr, nullptr, 1, 1, Fin(), k + 1);
-                } else {
-                    if (st == LSSP_AMD_OK) st = R.fin1(r, r, fr);
-                }
-                B.tl_after[j] = R.tl;
-            }
-            c->guard = nullptr;
-            LSSP_TRY(st);
-            LSSP_TRY(R.snap_issue(nq & 1));
-            queued += B.nb;
-            nq++;
-            return LSSP_AMD_OK;
-        };
-        it = 0;
-        LSSP_TRY(R.batch_begin(tol));
-        LSSP_TRY(push());
-        for (;;) {
-            if (queued < maxit) LSSP_TRY(push());  // runs while the batch before it is read
-            const Batch &B = bq[nr & 1];
-            LSSP_TRY(R.snap_wait(nr & 1));
-            nr++;
-            const int ran = std::max(1, std::min(B.nb, (int)R.h(S_NIT) - B.it0));
-            for (int q = 0; q < ran; q++) {
-                res = R.h(S_H + (B.it0 + q) % S_HB);
-                if (P.verb >= 1 && R.rank == 0)
-                    lprint("cg: itr: %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", it + q, res,
-                           (err_rel == 0 ? 0 : res / err_rel), (b_norm == 0 ? 0 : res / b_norm));
-            }
-            pending_rho = true;
-            if (R.h(S_DONE) != 0.0) {  // :109 held at iteration it + ran - 1
-                R.tl = B.tl_after[ran - 1];
-                it += ran - 1;
-                break;
-            }
-            it += B.nb;
-            if (nr == nq) break;  // maxit
+    constexpr int BATCH = CG_BATCH;  // iterations per batch (A/B: -DCG_BATCH)
+    lssp_amd_ctx *c = R.c;
+    // batched, one rank, tree reductions: each reduction's level 2 runs inside
+    // the vector update that consumes it (k_cg_fused): q.p (partial row 0, from
+    // the product) in the x/r update, r.r (row 1) in the next iteration's p
+    // update, whose finalize is held until then; the batch's last r.r on its own.
+    // Stamps are global iteration counts (FIN_CG_RES_RHO_B's S_DONE)
+    const bool fuse_l2 = batched && R.tree && c->nranks == 1 && R.n > 0;
+    Fin held;
+    bool have_held = false;  // within a batch only: its last iteration holds nothing
+    // one iteration :79-109 queued on the stream; more: another one of the same batch follows
+    auto enqueue = [&](int k, bool more) -> int {
+        if (R.M) {
+            LSSP_TRY(R.pc(z, r));                                  // :79
+            LSSP_TRY(R.dot1(z, r, R.fin(FIN_CG_RHO, 1, R.T())));  // :80
+        } else if (k == 0) {
+            LSSP_TRY(R.dot1(r, r, R.fin(FIN_CG_RHO, 1, R.T())));  // :80 (z == r)
         }
-    } else {
-        for (it = 0; it < maxit; it++) {
-            pending_rho = false;
-            if (R.M) {
-                LSSP_TRY(R.pc(z, r));                                   // :79
-                LSSP_TRY(R.dot1(z, r, R.fin(FIN_CG_RHO, 1, R.T())));   // :80
-            } else if (it == 0) {
-                LSSP_TRY(R.dot1(r, r, R.fin(FIN_CG_RHO, 1, R.T())));
-            }
+        if (have_held) {
+            // with the x update of the previous x/r pass (CGF_R): its stop test is stamped k
+            LSSP_TRY(launch_cg_fused(c, CGF_PX, R.n, x, p, nullptr, z, nullptr, 1, 1, held, k));
+        } else if (k == 0) {
+            LSSP_TRY(R.copy(z, p));  // :83-86
+        } else {
             Ew e;
-            if (it == 0) {
-                e.kind = K_COPY;  // :83-86
-                e.x = z;
-                e.out0 = p;
-            } else {
-                e.kind = K_CG_P;  // :88-92
-                e.x = z;
-                e.out0 = p;
-            }
+            e.kind = K_CG_P;  // :88-92
+            e.x = z;
+            e.out0 = p;
             LSSP_TRY(R.ew(e));
-            LSSP_TRY(R.spmv(EPI_MXY, 1, p, 0, nullptr, q, 1, p));        // :95
-            LSSP_TRY(R.fin1(q, p, R.fin(FIN_CG_ALPHA, 1, R.T())));      // :96-99
-            e = Ew();
+        }
+        have_held = false;
+        LSSP_TRY(R.spmv(EPI_MXY, 1, p, 0, nullptr, q, 1, p));  // :95
+        const Fin fa = R.fin(FIN_CG_ALPHA, 1, R.T());          // :96-99
+        if (fuse_l2) {
+            // r only: x += alpha p (:102) rides with the next p pass, or the batch's CGF_X
+            LSSP_TRY(launch_cg_fused(c, CGF_R, R.n, x, p, r, nullptr, q, 0, 1, fa));
+        } else {
+            LSSP_TRY(R.fin1(q, p, fa));
+            Ew e;
             e.kind = K_CG_XR;  // :101-104
             e.out0 = x;
             e.x = p;
@@ -668,27 +599,44 @@ int cg(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *
             e.r0a = r;
             e.r0b = r;
             LSSP_TRY(R.ew(e));
-            if (R.M) {
-                LSSP_TRY(R.fin1(r, r, R.fin(FIN_CG_RES, 1, R.T())));  // :106
-            } else {
-                int t0 = R.T(), t1 = R.T();
-                LSSP_TRY(R.fin1(r, r, R.fin(FIN_CG_RES_RHO, 1, t0, t1)));  // :106, next :80 (z == r)
-                pending_rho = true;
-            }
+        }
+        if (!batched) return R.fin1(r, r, R.fin(FIN_CG_RES, 1, R.T()));  // :106
+        int t0 = R.T(), t1 = R.T();
+        const Fin fr = R.fin(FIN_CG_RES_RHO_B, 1, t0, t1);  // :106-109, next :80
+        if (!fuse_l2) return R.fin1(r, r, fr);
+        if (more) {
+            held = fr;
+            have_held = true;
+            return LSSP_AMD_OK;
+        }
+        LSSP_TRY(launch_reduce_tree(c, num_chunks(R.n), 1, fr, 1));
+        return launch_cg_fused(c, CGF_X, R.n, x, p, nullptr, nullptr, nullptr, 1, 1, Fin(), k + 1);
+    };
+    if (batched) {
+        it = 0;
+        auto queue = [&](int k, int j, Run::Batch &B) { return enqueue(k, j + 1 < B.nb); };
+        auto read = [&](const Run::Batch &B, int ran, double done, bool &stop) -> int {
+            for (int i = 0; i < ran; i++) print_itr(R, P, "cg", it + i, R.hist(B, i), err_rel, b_norm);
+            res = R.hist(B, ran - 1);
+            pending_rho = true;
+            stop = done != 0.0;  // :109 held at iteration it + ran - 1
+            if (stop) R.tl = B.tl_after[ran - 1];
+            it += stop ? ran - 1 : B.nb;
+            return LSSP_AMD_OK;
+        };
+        LSSP_TRY(R.batches<BATCH>(tol, maxit, queue, read));
+    } else {
+        for (it = 0; it < maxit; it++) {
+            LSSP_TRY(enqueue(it, false));
             LSSP_TRY(R.sync(0, 16));
             res = R.h(S_RES);
-            if (P.verb >= 1 && R.rank == 0)
-                lprint("cg: itr: %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", it, res,
-                       (err_rel == 0 ? 0 : res / err_rel), (b_norm == 0 ? 0 : res / b_norm));
+            print_itr(R, P, "cg", it, res, err_rel, b_norm);
             if (res <= tol) break;  // :109
         }
     }
-    if (pending_rho) R.tl--;
+    if (pending_rho) R.tl--;  // the fused next-iteration rho1 is not part of the reference's run
     if (it < maxit) it += 1;
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("cg: total iteration: %d\n", it);
-        lprint("cg: total time: %g\n", wall_time() - t_start);
-    }
+    print_footer(R, P, "cg", it, t_start);
     *nits = it;
     *res_out = res;
     return LSSP_AMD_OK;
@@ -737,11 +685,8 @@ struct Gm {
         if (P.verb >= 2 && R.rank == 0) {
             lprint("%s: restart parameter m: %d\n", name, mk);
             if (aug) lprint("%s: aug k: %d\n", name, auk);
-            lprint("%s: maximal iteration: %d\n", name, maxit);
-            lprint("%s: tolerance abs: %g\n", name, tol_abs);
-            lprint("%s: tolerance rel: %g\n", name, tol_rel);
-            lprint("%s: tolerance rbn: %g\n", name, tol_rb);
         }
+        print_header(R, P, name, maxit, tol_abs, tol_rel, tol_rb);
         wj = R.vec();
         rg = R.vec();
         V = R.vec(R.nx * (long)mmax);
@@ -775,9 +720,7 @@ struct Gm {
         done = beta <= tol_abs;
         if (done) return LSSP_AMD_OK;
         err_rel = beta;
-        tol = tol_rel * err_rel;
-        if (tol < tol_abs) tol = tol_abs;
-        if (tol < tol_rb) tol = tol_rb;
+        tol = stop_scale(tol_rel, tol_abs, tol_rb, err_rel);
         rtol = tol / beta;
         return LSSP_AMD_OK;
     }
@@ -870,14 +813,7 @@ struct Gm {
         e.out0 = dst;
         return R.ew(e);
     }
-    int copy(const double *src, double *dst)  // lssp_vec_copy
-    {
-        Ew e;
-        e.kind = K_COPY;
-        e.x = src;
-        e.out0 = dst;
-        return R.ew(e);
-    }
+    int copy(const double *src, double *dst) { return R.copy(src, dst); }
     int divs(double *v, int sidx)  // v /= the device scalar sidx: the reference's inline division loops
     {
         Ew e;
@@ -886,13 +822,7 @@ struct Gm {
         e.sidx = sidx;
         return R.ew(e);
     }
-    void footer() const
-    {
-        if (P.verb >= 2 && R.rank == 0) {
-            lprint("%s: total iteration: %d\n", name, inner);
-            lprint("%s: total time: %g\n", name, wall_time() - t_start);
-        }
-    }
+    void footer() const { print_footer(R, P, name, inner, t_start); }
     int result(int *nits, double *res_out) const
     {
         *nits = inner;
@@ -1332,17 +1262,6 @@ struct L1K {
     }
 };
 
-void tol_setup(const lssp_amd_solve_params &P, double nrm2, double bnorm_rb, double &tol)
-{
-    // tol = nrm2*rtol; alpha = ||b||*rb; tol = max(tol, atol, alpha)  (e.g. solver-cgs.cxx:41-44)
-    double tol_rel, tol_abs;
-    int maxit;
-    defaults(P, tol_rel, tol_abs, maxit);
-    tol = nrm2 * tol_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < bnorm_rb) tol = bnorm_rb;
-}
-
 #define L1_DONE()                      \
     do {                               \
         K.flush();                     \
@@ -1367,7 +1286,7 @@ int cgs(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int 
     nrm2 = ires = K.norm(r);
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.copy(rtld, r);
     K.set(q, 0);
     K.set(p, 0);
@@ -1412,7 +1331,7 @@ int cr(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int *
     iter = 1;
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();  // nits = iter = 1 (:31-35, :105)
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.pc(p, r);
     K.mxy(p, q);
     K.copy(z, p);
@@ -1453,7 +1372,7 @@ int crs(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int 
     iter = 1;
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.copy(p, r);
     K.mxy(p, rtld);
     rho_old = 1.0;
@@ -1501,7 +1420,7 @@ int bicrstab(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
     iter = 1;
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.copy(p, r);
     K.mxy(p, rtld);
     K.pc(z, r);
@@ -1578,7 +1497,7 @@ int bicgsafe(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
     iter = 1;
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.copy(rtld, r);
     K.pc(mr, r);
     K.mxy(mr, amr);
@@ -1639,7 +1558,7 @@ int bicrsafe(Run &R, const lssp_amd_solve_params &P, double *x, const double *b,
     iter = 1;
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.copy(rtld, r);
     K.mxy(rtld, artld);
     K.pc(mr, r);
@@ -1709,7 +1628,7 @@ int gpbi(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int
         L1_DONE();
     }
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     if (cr_) {
         K.copy(p, r);
         K.mxy(p, rtld);
@@ -1780,12 +1699,7 @@ int qmrcgstab(Run &R, const lssp_amd_solve_params &P, double *xk, const double *
     double tol_rel, tol_abs, tol_rb = P.tol_rb;
     int itr_max, itr_out;
     defaults(P, tol_rel, tol_abs, itr_max);
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("qmrcgstab: maximal iteration: %d\n", itr_max);
-        lprint("qmrcgstab: tolerance abs: %g\n", tol_abs);
-        lprint("qmrcgstab: tolerance rel: %g\n", tol_rel);
-        lprint("qmrcgstab: tolerance rbn: %g\n", tol_rb);
-    }
+    print_header(R, P, "qmrcgstab", itr_max, tol_abs, tol_rel, tol_rb);
     double *rk = K.vec(), *r = K.vec(), *br0 = K.vec(), *pk = K.vec(), *vk = K.vec(), *sk = K.vec();
     double *dk = K.vec(), *tk = K.vec(), *bdk = K.vec(), *bxk = K.vec();
     double rho = 1, prho, alpha = 1, beta, omega = 1, theta = 0., btheta, b_eta, eta = 0., tau, btau;
@@ -1800,10 +1714,7 @@ int qmrcgstab(Run &R, const lssp_amd_solve_params &P, double *xk, const double *
         *res_out = residual;
         return LSSP_AMD_OK;
     }
-    tol = residual * tol_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
-    tol = tol / residual;
+    tol = stop_scale(tol_rel, tol_abs, tol_rb, residual) / residual;
     K.pc(rk, tk);
     K.copy(br0, rk);
     K.set(pk, 0);
@@ -1853,11 +1764,8 @@ int qmrcgstab(Run &R, const lssp_amd_solve_params &P, double *xk, const double *
     }
     if (!K.ok()) return K.st;
     if (itr_out < itr_max) itr_out += 1;
-    if (P.verb >= 2 && R.rank == 0) {  // solver-qmrcgstab.cxx:178-183
-        lprint("qmrcgstab: total iteration: %d\n", itr_out);
-        lprint("qmrcgstab: total time: %g\n", wall_time() - t_start);
-        lprint("qmrcgstab: absolute error (residual): %g\n", residual);
-    }
+    print_footer(R, P, "qmrcgstab", itr_out, t_start);  // solver-qmrcgstab.cxx:178-183
+    if (P.verb >= 2 && R.rank == 0) lprint("qmrcgstab: absolute error (residual): %g\n", residual);
     *nits = itr_out;
     *res_out = residual;
     return LSSP_AMD_OK;
@@ -1882,7 +1790,7 @@ int tfqmr(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, in
         L1_DONE();
     }
     alpha = K.norm(b) * P.tol_rb;
-    tol_setup(P, nrm2, alpha, tol);
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);  // e.g. solver-cgs.cxx:41-44
     K.copy(rtld, r);
     K.copy(p, r);
     K.copy(u, r);
@@ -1947,13 +1855,8 @@ int orthomin(Run &R, const lssp_amd_solve_params &P, double *x, const double *rh
     defaults(P, tol_rel, tol_abs, itr_max);
     int k = P.restart < 0 ? DEF_RESTART : P.restart;
     if (k == 0) return LSSP_AMD_EINVAL;  // the reference divides by it (:102)
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("orthomin: k parameter m: %d\n", k);
-        lprint("orthomin: maximal iteration: %d\n", itr_max);
-        lprint("orthomin: tolerance abs: %g\n", tol_abs);
-        lprint("orthomin: tolerance rel: %g\n", tol_rel);
-        lprint("orthomin: tolerance rbn: %g\n", tol_rb);
-    }
+    if (P.verb >= 2 && R.rank == 0) lprint("orthomin: k parameter m: %d\n", k);
+    print_header(R, P, "orthomin", itr_max, tol_abs, tol_rel, tol_rb);
     double *z = K.vec(), *r = K.vec(), *s = K.vec(), *sd = K.vec();
     std::vector<double *> p(k), q(k);
     std::vector<double> b_j(k), c_j(k);
@@ -1977,9 +1880,7 @@ int orthomin(Run &R, const lssp_amd_solve_params &P, double *x, const double *rh
         return LSSP_AMD_OK;
     }
     err_rel = beta;
-    tol = tol_rel * err_rel;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < tol_rb) tol = tol_rb;
+    tol = stop_scale(tol_rel, tol_abs, tol_rb, err_rel);
     for (itr_out = 0; itr_out < itr_max; itr_out++) {
         K.mxy(sd, s);
         j = itr_out % k;
@@ -2006,16 +1907,11 @@ int orthomin(Run &R, const lssp_amd_solve_params &P, double *x, const double *rh
         K.resid(x, rhs, z);
         beta = K.norm(z);
         if (!K.ok()) return K.st;
-        if (P.verb >= 1 && R.rank == 0)
-            lprint("orthomin: itr: %5d, abs res: %.6e, rel res: %.6e, rbn: %.6e\n", itr_out, beta,
-                   (err_rel == 0 ? 0 : beta / err_rel), (b_norm == 0 ? 0 : beta / b_norm));
+        print_itr(R, P, "orthomin", itr_out, beta, err_rel, b_norm);
         if (beta <= tol) break;
     }
     if (itr_out < itr_max) itr_out += 1;
-    if (P.verb >= 2 && R.rank == 0) {
-        lprint("orthomin: total iteration: %d\n", itr_out);
-        lprint("orthomin: total time: %g\n", wall_time() - t_start);
-    }
+    print_footer(R, P, "orthomin", itr_out, t_start);
     *nits = itr_out;
     *res_out = beta;
     return LSSP_AMD_OK;
@@ -2052,10 +1948,8 @@ int bicgstabl(Run &R, const lssp_amd_solve_params &P, double *x, const double *b
     iter = 0;
     nrm2 = ires = K.norm(r[0]);
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
-    tol = nrm2 * tol_rel;
     alpha = K.norm(b) * tol_rb;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < alpha) tol = alpha;
+    tol = stop_scale(tol_rel, tol_abs, alpha, nrm2);
     alpha = 0.0;
     omega = 1.0;
     rho0 = 1.0;
@@ -2210,10 +2104,8 @@ int idrs(Run &R, const lssp_amd_solve_params &P, double *x, const double *b, int
     K.resid(x, b, r);
     nrm2 = ires = K.norm(r);
     if (!K.ok() || nrm2 <= tol_abs) L1_DONE();
-    tol = nrm2 * tol_rel;
     h = K.norm(b) * tol_rb;
-    if (tol < tol_abs) tol = tol_abs;
-    if (tol < h) tol = h;
+    tol = stop_scale(tol_rel, tol_abs, h, nrm2);
     if (!K.ok()) return K.st;
     {
         const long n = R.n, ng = R.A->n_global > 0 ? R.A->n_global : R.n, r0 = R.A->row0;
