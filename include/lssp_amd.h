@@ -567,6 +567,9 @@ int lssp_amd_bilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_ma
  * outside [0, nnz) returns LSSP_AMD_EINVAL, NULL arguments too, with everything
  * a caller can read unchanged: nothing is written before the check has passed,
  * and nothing can refuse after it (scalar ILU(0) replaces tiny pivots).
+ * Afterwards lssp_amd_ilu_get_schedule answers what it answers for a fresh
+ * lssp_amd_ilu_create of the new values, its header word "unit" included (one
+ * flag word comes back from the U sweep's refill for it).
  * The first call builds a plan kept until lssp_amd_ilu_destroy: the factor
  * pattern with one flag byte per entry (matrix entry, fill, inserted
  * diagonal), a factor value buffer, the reciprocal pivots, each row's diagonal

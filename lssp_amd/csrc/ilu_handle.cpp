@@ -358,13 +358,19 @@ int lssp_amd_iluk_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat 
         LSSP_TRY(clk.mark("scatter"));
         LSSP_TRY(refactor_levels(c, p, M->n));
         LSSP_TRY(clk.mark("numeric"));
+        int nonunit = 1;
         if (packets) {
+            // d_flag is 0 here (iluk_match accepted the pattern); the U refill ORs it
+            // when a pivot is not 1.0, which lssp_amd_ilu_get_schedule reports as a
+            // fresh create would
             LSSP_TRY(launch_pk6_refill_scalar(c, M->lower, false, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
-            LSSP_TRY(launch_pk6_refill_scalar(c, M->upper, true, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
+            LSSP_TRY(launch_pk6_refill_scalar(c, M->upper, true, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx, p.d_flag));
+            LSSP_HIP(hipMemcpyAsync(&nonunit, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         } else {
             LSSP_TRY(launch_linefill_refill(c, M->line, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
         }
         LSSP_HIP(hipStreamSynchronize(c->stream));
+        if (packets) M->upper.bp_unit = nonunit ? 0 : 1;
         LSSP_TRY(clk.mark("refill"));
         // the device factors are ahead of Lx / Ux now, and of the sync-free arrays a
         // single sweep built from those: the next reader refreshes the host

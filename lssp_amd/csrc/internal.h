@@ -661,9 +661,11 @@ int iluk_match(lssp_amd_ctx *c, const RefactorPlan &p, int n, int nnz, const int
 int iluk_scatter(lssp_amd_ctx *c, RefactorPlan &p, int n, const int *dAp, const double *dAx);
 int refactor_levels(lssp_amd_ctx *c, RefactorPlan &p, int n);
 // trisolve.hip: launch_pk6_refill for a scalar factor F (dpos: each row's
-// diagonal position); the U sweep's records also get D = the stored pivot
+// diagonal position); the U sweep's records also get D = the stored pivot, and
+// *nonunit (device, zeroed by the caller; may be null) is ORed with 1 when one
+// of those pivots is not exactly 1.0
 int launch_pk6_refill_scalar(lssp_amd_ctx *c, const TriSched &t, bool upper, int n, const int *Fp, const int *Fj,
-                             const int *dpos, const double *Fx);
+                             const int *dpos, const double *Fx, int *nonunit = nullptr);
 // linefill.hip: both coefficient streams of a k_linef factor rewritten from
 // the factored values Fx on the pattern (Fp, Fj); every slot is written
 int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const int *dpos,

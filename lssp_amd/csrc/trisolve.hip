@@ -715,29 +715,38 @@ int launch_pk6_refill(lssp_amd_ctx *c, const TriSched &t, bool upper, int bs, in
 // The same walk for a scalar ILUK factor F (lssp_amd_iluk_refactor): the block
 // pattern is F itself, and the U sweep's records also take D = the stored pivot
 // (iluk_pk6_row).  BILUK records (D = 1.0 throughout) keep k_pk6_refill.
+// nonunit (U sweep): *nonunit |= 1 when some stored pivot is not exactly 1.0,
+// what the schedule's header reports as "unit" (TriSched::bp_unit).
 __global__ __launch_bounds__(256) void k_pk6_refill_scalar(int npk, int EP, int upper, int n,
                                                            const int4 *__restrict__ desc, uint32_t *__restrict__ rec,
                                                            const int *__restrict__ Fp, const int *__restrict__ Fj,
-                                                           const int *__restrict__ dpos, const double *__restrict__ Fx)
+                                                           const int *__restrict__ dpos, const double *__restrict__ Fx,
+                                                           int *__restrict__ nonunit)
 {
     const int lane = threadIdx.x & 63;
+    bool other = false;
     for (long p = blockIdx.x * 4L + (threadIdx.x >> 6); p < npk; p += (long)gridDim.x * 4) {
         const int4 d = desc[p];
         const int nr = d.z & 0x3ff;
         uint32_t *w = rec + 4L * d.x;
         const uint32_t *ROW = w + pk6_layout(EP, nr).row;
-        for (int r = lane; r < nr; r += 64) iluk_pk6_row(w, EP, nr, r, (int)ROW[r], upper != 0, n, Fp, Fj, dpos, Fx);
+        for (int r = lane; r < nr; r += 64) {
+            const int row = (int)ROW[r];
+            iluk_pk6_row(w, EP, nr, r, row, upper != 0, n, Fp, Fj, dpos, Fx);
+            if (upper && row >= 0 && row < n) other |= Fx[dpos[row]] != 1.0;
+        }
     }
+    if (other && nonunit) atomicOr(nonunit, 1);
 }
 
 int launch_pk6_refill_scalar(lssp_amd_ctx *c, const TriSched &t, bool upper, int n, const int *Fp, const int *Fj,
-                             const int *dpos, const double *Fx)
+                             const int *dpos, const double *Fx, int *nonunit)
 {
     if (t.pk6_n <= 0) return LSSP_AMD_EUNSUPPORTED;
     const unsigned grid = (unsigned)std::min<long>(((long)t.pk6_n + 3) / 4, 16384);
     k_pk6_refill_scalar<<<grid, 256, 0, c->stream>>>(t.pk6_n, t.pk6_ep, upper ? 1 : 0, n,
                                                      reinterpret_cast<const int4 *>(t.pk6_desc), t.pk6_rec, Fp, Fj, dpos,
-                                                     Fx);
+                                                     Fx, nonunit);
     LSSP_HIP(hipGetLastError());
     return LSSP_AMD_OK;
 }
