@@ -410,11 +410,13 @@ int lssp_amd_bcsr_to_csr(lssp_amd_ctx *ctx, int nbrows, int nbcols, int bs, int 
  *      (lssp_amd_ilu_from_factors_dev).  ILUK of any other one-block matrix
  *      with sorted rows, at any level, is made on the device as well, symbolic
  *      factorization included; lssp_amd_pc_create_dev is the one call that
- *      routes to all of them.
+ *      routes to all of them.  BILUK with blocks up to 8 x 8 is made on the
+ *      device from the handle too (lssp_amd_bilu_create_dev).
  *      What still goes through the host: every other ILU setup
  *      (lssp_amd_ilu_create / lssp_amd_bilu_create take host arrays, as the
  *      reference factors on the host; download the CSR for them:
- *      block-Jacobi, BILUK, a row without its diagonal), and the
+ *      block-Jacobi, BILUK with blocks beyond 8 x 8 or a block row without
+ *      its diagonal block, a row without its diagonal), and the
  *      sliced copy of a windowed matrix (see lssp_amd_mat_from_device).  Both
  *      only when the PATTERN is new: new values on the same pattern stay on the
  *      device (lssp_amd_mat_update_values, lssp_amd_ilu_refactor /
@@ -722,6 +724,53 @@ int lssp_amd_ilut_capacity(void);
  * schedules).  Returns when the stream has finished. */
 int lssp_amd_pc_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p, int blk,
                            lssp_amd_ilu **out);
+/* lssp_amd_bilu_create for a matrix that lives in HBM: BILUK, the reference's
+ * block ILU(level) on bs x bs blocks, made on the device from the handle A.
+ * Eligible: a single-rank square A, n % bs == 0, 1 <= bs <= 8 (the device numeric
+ * path), every row's columns strictly ascending inside [0, n), every block row
+ * holding at least one entry in its diagonal block.  A negative level means the
+ * default, 1; levels up to 254 are accepted.
+ * The route: the rows are checked; the block graph -- each block row's sorted
+ * distinct block columns, a bs-way merge of its bs rows -- is built by a count
+ * pass, a scan and a fill pass, one block row per lane; at level >= 1 the
+ * symbolic ILU(level) of that graph is lssp_amd_pc_create_dev's, one wavefront per
+ * block row (the reference's level rule); the level lists of the block rows come
+ * from the device level pass; the values go through lssp_amd_bilu_refactor's own
+ * scatter, numeric and U-scaling kernels; the factored blocks are expanded to the
+ * point factors L and U in HBM, and both packet schedules are built there
+ * (lssp_amd_ilu_get_schedule answers origin 1).  No array of A and no factor
+ * array crosses to the host: flag words, block and entry counts, Bp[nb] and the
+ * level lists' offsets come back.  The handle owns what it needs: A may be
+ * destroyed on return.
+ * The handle is bitwise lssp_amd_bilu_create(A's arrays, level, bs)'s in
+ * lssp_amd_ilu_apply / _apply_async + _check / _trisolve / lssp_amd_solve,
+ * lssp_amd_ilu_info, _get_factors and _get_diag, and in lssp_amd_ilu_get_schedule
+ * apart from origin.  It is born with lssp_amd_bilu_refactor's plan (16 bs^2 + 10 B
+ * per block and 8 bs^2 + 12 B per block row of device memory): the refactor is
+ * eligible at once and builds nothing.  The host copies of L, U, the inverses
+ * and the block pattern are made by the first call that reads them, from the
+ * plan.  Factors beyond the device schedule builder (a strict row beyond 24
+ * entries, e.g. bs = 8 at level 1 on a 7-point block grid, or the packet limits)
+ * take the host-built schedules, sync-free fallback included, from one download
+ * of the factored blocks; such a handle keeps no plan and lssp_amd_bilu_refactor
+ * refuses it, as it refuses the host-made one.
+ * LSSP_AMD_EUNSUPPORTED, with *out == NULL, nothing left allocated, A and ctx
+ * usable: bs 9..32 (lssp_amd_bilu_create factors those on the host), a
+ * distributed A, a row whose columns are not strictly ascending inside [0, n)
+ * (lssp_amd_csr_sort_columns_dev sorts one), a block row without its diagonal
+ * block -- lssp_amd_bilu_create gives such a row the identity as its inverse;
+ * that path is not reproduced here, at any level --, a working block row beyond
+ * lssp_amd_ilut_capacity() blocks on one side of the diagonal, level > 254, a
+ * block pattern beyond INT_MAX blocks or bs^2 * blocks + n beyond INT_MAX.
+ * LSSP_AMD_EINVAL: NULL arguments, nrows != ncols, n % bs != 0, bs outside 1..32,
+ * an exactly singular diagonal block (the device numeric path's flag).
+ * LSSP_AMD_ETIMEOUT: a bounded wait of the symbolic or the level pass expired.
+ * LSSP_AMD_EHIP: a HIP error part-way, everything freed.  LSSP_AMD_SETUP_TIMES=1
+ * prints the phases (check, block graph, graph check, symbolic, pack, levels,
+ * scatter, numeric BILU(0), U scaling, expansion, then per side the schedule
+ * builder's; on the host route download, schedules).  Returns when the stream
+ * has finished. */
+int lssp_amd_bilu_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int level, int bs, lssp_amd_ilu **out);
 
 /* ---- synthetic inputs (example/exam.cxx:4-59 and its 7-pt analogue) ------ */
 long lssp_amd_poisson_nnz(int dim, int N);

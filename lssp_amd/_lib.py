@@ -118,6 +118,7 @@ SIGNATURES = {
     "lssp_amd_ilu_get_schedule": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lssp_amd_ilut_capacity": (_ci, []),
     "lssp_amd_pc_create_dev": (_ci, [_vp, _vp, _ci, _ci, _cd, _ci, _ci, _pvp]),
+    "lssp_amd_bilu_create_dev": (_ci, [_vp, _vp, _ci, _ci, _pvp]),
     "lssp_amd_poisson_nnz": (_cl, [_ci, _ci]),
     "lssp_amd_poisson_rows": (_ci, [_ci, _ci, _cl, _cl, _vp, _vp, _vp]),
 }

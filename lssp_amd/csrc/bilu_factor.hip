@@ -24,11 +24,23 @@
 // launches on buffers that stay on the device: A's values scattered into the
 // kept block pattern, the block graph compared, k_bilu0_level, the U blocks
 // scaled, the packet records refilled (trisolve.hip k_pk6_refill).
+//
+// lssp_amd_bilu_create_dev (third part) makes the handle from a
+// matrix in HBM: the block graph (k_bilu_graph), the symbolic ILU(k) of that
+// graph and its level lists (iluk_symbolic.hip, unchanged), the refactor's own
+// scatter / numeric / commit launches on a plan filled on the device, and the
+// expansion of the committed blocks to the point factors (k_bilu_expand) that
+// the device schedule builder reads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
+#include <cstring>
 #include <vector>
 
+#include <rocprim/device/device_scan.hpp>
+
+#include "bilu_create_dev.h"
 #include "bilu_dev.h"
 #include "bilu_refactor_dev.h"
 #include "internal.h"
@@ -323,6 +335,37 @@ __global__ __launch_bounds__(256) void k_bilu_commit(long nblk, const int *__res
     }
 }
 
+static unsigned bilu_grid(long items)
+{
+    return (unsigned)std::max<long>(1, std::min<long>((items + 255) / 256, 16384));
+}
+
+// k_bilu_commit<bs> on the plan's buffers: the refactor's and the device create's
+static int bilu_commit_launch(lssp_amd_ctx *c, BiluPlan &p)
+{
+    const int bs2 = p.bs * p.bs;
+    switch (p.bs) {
+#define LSSP_BCOMMIT(B)                                                                                      \
+    case B:                                                                                                  \
+        k_bilu_commit<B><<<bilu_grid(p.nblk * bs2), 256, 0, c->stream>>>(p.nblk, p.d_Brow, p.d_Bj, p.d_Bx, p.d_inv, \
+                                                                         p.d_Fx);                            \
+        break;
+        LSSP_BCOMMIT(1)
+        LSSP_BCOMMIT(2)
+        LSSP_BCOMMIT(3)
+        LSSP_BCOMMIT(4)
+        LSSP_BCOMMIT(5)
+        LSSP_BCOMMIT(6)
+        LSSP_BCOMMIT(7)
+        LSSP_BCOMMIT(8)
+#undef LSSP_BCOMMIT
+    default:
+        return LSSP_AMD_EUNSUPPORTED;
+    }
+    LSSP_HIP(hipGetLastError());
+    return LSSP_AMD_OK;
+}
+
 void bilu_plan_free(BiluPlan *p)
 {
     if (!p) return;
@@ -395,15 +438,14 @@ int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A
     BiluPlan &p = *M->brf;
     const int n = M->n, bs = p.bs, bs2 = bs * bs;
     const long nblk = p.nblk;
-    auto grid = [](long items) { return (unsigned)std::max<long>(1, std::min<long>((items + 255) / 256, 16384)); };
     int flag = 0;
     // 1. zero, scatter; 2. graph compare -- on scratch only
     LSSP_HIP(hipMemsetAsync(p.d_Bx, 0, sizeof(double) * std::max<long>(nblk, 1) * bs2, c->stream));
     LSSP_HIP(hipMemsetAsync(p.d_hit, 0, std::max<long>(nblk, 1), c->stream));
     LSSP_HIP(hipMemsetAsync(p.d_flag, 0, sizeof(int) * 2, c->stream));
-    k_bilu_scatter<<<grid(n), 256, 0, c->stream>>>(n, bs, A->nnz, A->Ap, A->Aj, A->Ax, p.d_Bp, p.d_Bj, p.d_Bx, p.d_hit,
-                                                  p.d_flag);
-    k_bilu_graph_cmp<<<grid(nblk), 256, 0, c->stream>>>(nblk, p.d_hit, p.d_in, p.d_flag);
+    k_bilu_scatter<<<bilu_grid(n), 256, 0, c->stream>>>(n, bs, A->nnz, A->Ap, A->Aj, A->Ax, p.d_Bp, p.d_Bj, p.d_Bx,
+                                                       p.d_hit, p.d_flag);
+    k_bilu_graph_cmp<<<bilu_grid(nblk), 256, 0, c->stream>>>(nblk, p.d_hit, p.d_in, p.d_flag);
     LSSP_HIP(hipGetLastError());
     LSSP_HIP(hipMemcpyAsync(&flag, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));
@@ -417,24 +459,7 @@ int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A
     if (flag) return LSSP_AMD_EINVAL;  // singular diagonal block
     LSSP_TRY(clk.mark("numeric BILU(0)"));
     // 4. - 6.: the committed values, the record streams, the inverses
-    switch (bs) {
-#define LSSP_BCOMMIT(B)                                                                                        \
-    case B:                                                                                                    \
-        k_bilu_commit<B><<<grid(nblk * bs2), 256, 0, c->stream>>>(nblk, p.d_Brow, p.d_Bj, p.d_Bx, p.d_inv, p.d_Fx); \
-        break;
-        LSSP_BCOMMIT(1)
-        LSSP_BCOMMIT(2)
-        LSSP_BCOMMIT(3)
-        LSSP_BCOMMIT(4)
-        LSSP_BCOMMIT(5)
-        LSSP_BCOMMIT(6)
-        LSSP_BCOMMIT(7)
-        LSSP_BCOMMIT(8)
-#undef LSSP_BCOMMIT
-    default:
-        return LSSP_AMD_EUNSUPPORTED;
-    }
-    LSSP_HIP(hipGetLastError());
+    LSSP_TRY(bilu_commit_launch(c, p));
     LSSP_TRY(clk.mark("U scaling"));
     LSSP_TRY(launch_pk6_refill(c, M->lower, false, bs, p.nb, p.d_Bp, p.d_Bj, p.d_first, p.d_Fx));
     LSSP_TRY(launch_pk6_refill(c, M->upper, true, bs, p.nb, p.d_Bp, p.d_Bj, p.d_first, p.d_Fx));
@@ -446,30 +471,291 @@ int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A
 }
 
 // Lx / Ux / Dinv from the committed device values: one download of the block
-// buffer and of the inverses, then bilu_expand (the U blocks are scaled already)
+// buffer and of the inverses, then bilu_expand (the U blocks are scaled already).
+// A handle lssp_amd_bilu_create_dev made has no host copies at all yet
+// (host_missing): its block pattern and graph flags come down from the plan
+// first, and bilu_expand's patterns are kept as well.
 int bilu_refactor_host_factors(lssp_amd_ilu *M)
 {
     if (!M->host_stale || !M->brf) return LSSP_AMD_OK;
     lssp_amd_ctx *c = M->ctx;
     const BiluPlan &p = *M->brf;
+    const size_t nblk = (size_t)p.nblk;
+    if (M->host_missing) {
+        std::vector<int> Bp((size_t)p.nb + 1), Bj(nblk);
+        std::vector<unsigned char> in(nblk);
+        LSSP_HIP(hipMemcpyAsync(Bp.data(), p.d_Bp, sizeof(int) * Bp.size(), hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(Bj.data(), p.d_Bj, sizeof(int) * nblk, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipMemcpyAsync(in.data(), p.d_in, nblk, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        M->bBp = std::move(Bp);
+        M->bBj = std::move(Bj);
+        M->bIn = std::move(in);
+    }
     HostBCSR T;
     T.nb = p.nb;
     T.bs = p.bs;
     T.Bp = M->bBp;
     T.Bj = M->bBj;
-    T.Bx.resize((size_t)p.nblk * p.bs * p.bs);
-    std::vector<double> inv(M->Dinv.size());
+    T.Bx.resize(nblk * p.bs * p.bs);
+    std::vector<double> inv((size_t)p.nb * p.bs * p.bs);
     LSSP_HIP(hipMemcpyAsync(T.Bx.data(), p.d_Fx, sizeof(double) * T.Bx.size(), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipMemcpyAsync(inv.data(), M->d_Dinv, sizeof(double) * inv.size(), hipMemcpyDeviceToHost, c->stream));
     LSSP_HIP(hipStreamSynchronize(c->stream));
     HostCSR L, U;
     bilu_expand(T, inv, L, U, true);
-    if (L.Ax.size() != M->Lx.size() || U.Ax.size() != M->Ux.size()) return LSSP_AMD_EINVAL;
+    if (M->host_missing) {
+        if (L.Ax.size() != (size_t)M->dev_nnzL || U.Ax.size() != (size_t)M->dev_nnzU) return LSSP_AMD_EINVAL;
+        M->Lp = std::move(L.Ap);
+        M->Lj = std::move(L.Aj);
+        M->Up = std::move(U.Ap);
+        M->Uj = std::move(U.Aj);
+        M->host_missing = false;
+    } else if (L.Ax.size() != M->Lx.size() || U.Ax.size() != M->Ux.size()) {
+        return LSSP_AMD_EINVAL;
+    }
     M->Lx = std::move(L.Ax);
     M->Ux = std::move(U.Ax);
     M->Dinv = std::move(inv);
     M->host_stale = false;
     return LSSP_AMD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// lssp_amd_bilu_create_dev: the handle's plan and point factors from a matrix in
+// HBM
+// ---------------------------------------------------------------------------
+// k_ilut_check's rule (ilut_factor.hip) without the scalar diagonal, which BILUK
+// does not need: Ap starts at 0, ends at nnz and never descends; every row's
+// columns ascend strictly inside [0, n).  A row is read only when its range
+// lies inside [0, nnz].
+__global__ __launch_bounds__(256) void k_bilu_rows_check(int n, int nnz, const int *__restrict__ Ap,
+                                                         const int *__restrict__ Aj, int *__restrict__ flag)
+{
+    bool bad = false;
+    for (long r = blockIdx.x * 256L + threadIdx.x; r < n; r += (long)gridDim.x * 256) {
+        const int a = Ap[r], b = Ap[r + 1];
+        if (r == 0) bad |= a != 0;
+        if (r == n - 1) bad |= b != nnz;
+        if (a < 0 || b > nnz || b < a) {
+            bad = true;
+            continue;
+        }
+        int prev = -1;
+        for (int k = a; k < b; k++) {
+            const int col = Aj[k];
+            bad |= col <= prev || col >= n;
+            prev = col;
+        }
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// The block graph, one block row per lane (bilu_graph_row): the bs-way merge is
+// sequential inside a block row -- each step needs the smallest head -- so a wave
+// that owned one block row could keep only its bs <= 8 rows' lanes busy and
+// would pay a cross-lane minimum per block; with a block row per lane all 64
+// lanes merge, the cursors live in registers, and neighbouring lanes read
+// neighbouring rows of Aj, whose lines stay in cache from one step to the next
+// (k_bilu_scatter's argument).  Gj == nullptr: the count pass -- cnt[i], cnt[nb]
+// = 0 for the exclusive scan -- which also raises *flag for a block row without
+// its diagonal block; else the fill pass into Gj + Gp[i].
+__global__ __launch_bounds__(256) void k_bilu_graph(int nb, int bs, const int *__restrict__ Ap,
+                                                    const int *__restrict__ Aj, const int *__restrict__ Gp,
+                                                    int *__restrict__ Gj, int *__restrict__ cnt,
+                                                    int *__restrict__ flag)
+{
+    bool bad = false;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i <= nb; i += (long)gridDim.x * 256) {
+        if (i == nb) {
+            if (!Gj) cnt[nb] = 0;
+            continue;
+        }
+        int diag = 0;
+        const int m = bilu_graph_row((int)i, bs, Ap, Aj, Gj ? Gj + Gp[i] : nullptr, &diag);
+        if (!Gj) cnt[i] = m;
+        bad |= !diag;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// per block row of the factor pattern: its blocks' block row (BiluPlan::d_Brow)
+// and how many blocks lie left / right of the diagonal block (slot nb: 0, for
+// the exclusive scans that place the rows of L and U)
+__global__ __launch_bounds__(256) void k_bilu_sides(int nb, const int *__restrict__ Bp, const int *__restrict__ Bj,
+                                                    const int *__restrict__ first, int *__restrict__ Brow,
+                                                    int *__restrict__ cl, int *__restrict__ cu)
+{
+    for (long i = blockIdx.x * 256L + threadIdx.x; i <= nb; i += (long)gridDim.x * 256) {
+        if (i == nb) {
+            cl[nb] = cu[nb] = 0;
+            continue;
+        }
+        const int s = Bp[i], e = Bp[i + 1], f = first[i];
+        for (int k = s; k < e; k++) Brow[k] = (int)i;
+        cl[i] = f - s;
+        cu[i] = e - f - (f < e && Bj[f] == (int)i ? 1 : 0);
+    }
+}
+
+// The expansion, one wave per block row (bilu_expand_blockrow): block row i's bs
+// rows of a point factor are one contiguous run of bs * (bs * blocks + 1)
+// entries, the lanes take consecutive entries of it, so Tj and Tx are written in
+// whole cache lines.  The reads of a block are strided by bs doubles, but a
+// block row's blocks are one contiguous piece of Fx of a few hundred bytes to a
+// few KiB that this wave alone reads, every line of it within one or two loads
+// of the wave: each line comes from L2 once and is then hit in the CU's cache,
+// which is what a staging copy in LDS would buy (at the price of a barrier per
+// block row and bank conflicts at stride bs), so there is none.
+__global__ __launch_bounds__(256) void k_bilu_expand(int nb, int bs, bool upper, const int *__restrict__ Bp,
+                                                     const int *__restrict__ Bj, const int *__restrict__ first,
+                                                     const int *__restrict__ before, const double *__restrict__ Fx,
+                                                     int *__restrict__ Tp, int *__restrict__ Tj,
+                                                     double *__restrict__ Tx)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long i = blockIdx.x * 4L + wave; i < nb; i += (long)gridDim.x * 4)
+        bilu_expand_blockrow(upper, bs, nb, (int)i, before[i], Bp, Bj, first, Fx, Tp, Tj, Tx, lane, 64);
+}
+
+static int bilu_scan_excl(lssp_amd_ctx *c, DevBufs &B, const int *in, int *out, size_t cnt)
+{
+    size_t bytes = 0;
+    char *tmp = nullptr;
+    LSSP_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0, cnt, rocprim::plus<int>(), c->stream));
+    LSSP_HIP(B.get(&tmp, bytes));
+    LSSP_HIP(rocprim::exclusive_scan(tmp, bytes, in, out, 0, cnt, rocprim::plus<int>(), c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));  // the scratch is freed next
+    B.drop(tmp);
+    return LSSP_AMD_OK;
+}
+
+namespace {
+// the symbolic pass's plan (iluk_symbolic_dev) and the split of the block pattern
+// the level pass reads: scratch of this create, freed on every path out of it
+struct BlockSymbolic {
+    lssp_amd_ctx *c;
+    RefactorPlan *rp = nullptr;
+    IlutDevFactors S;
+    ~BlockSymbolic()
+    {
+        (void)hipStreamSynchronize(c->stream);
+        iluk_split_free(&S);
+        refactor_plan_free(rp);
+    }
+};
+}  // namespace
+
+int bilu_create_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A, int level, int bs, IlutDevFactors *F,
+                       const std::function<int(const char *)> &mark)
+{
+    const int n = A->nrows, nnz = A->nnz, nb = n / bs, bs2 = bs * bs;
+    if (bs < 1 || bs > BILU_MAX_BS_DEV || n != nb * bs) return LSSP_AMD_EUNSUPPORTED;
+    if (nnz < nb) return LSSP_AMD_EUNSUPPORTED;  // some block row is empty: no diagonal block
+    DevBufs B;
+    int *flag = nullptr, *cnt = nullptr, *Gp = nullptr, *Gj = nullptr, h[2] = {1, 0};
+    LSSP_HIP(B.get(&flag, 4));
+    LSSP_HIP(hipMemsetAsync(flag, 0, 16, c->stream));
+    // 1. nothing of A is trusted before this
+    k_bilu_rows_check<<<bilu_grid(n), 256, 0, c->stream>>>(n, nnz, A->Ap, A->Aj, flag);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipMemcpyAsync(h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    if (h[0]) return LSSP_AMD_EUNSUPPORTED;  // an unsorted row, a repeated column, a column outside [0, n)
+    LSSP_TRY(mark("check"));
+    // 2. the block graph: count, scan, fill
+    LSSP_HIP(B.get(&cnt, (size_t)nb + 1));
+    LSSP_HIP(B.get(&Gp, (size_t)nb + 1));
+    k_bilu_graph<<<bilu_grid((long)nb + 1), 256, 0, c->stream>>>(nb, bs, A->Ap, A->Aj, nullptr, nullptr, cnt, flag + 1);
+    LSSP_HIP(hipGetLastError());
+    LSSP_TRY(bilu_scan_excl(c, B, cnt, Gp, (size_t)nb + 1));
+    h[0] = 1;
+    LSSP_HIP(hipMemcpyAsync(h, flag + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h + 1, Gp + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    if (h[0]) return LSSP_AMD_EUNSUPPORTED;  // a block row without its diagonal block
+    const int ng = h[1];
+    if (ng < nb || ng > nnz) return LSSP_AMD_EHIP;  // (every block holds an entry of A)
+    if ((long)ng * bs2 + n > (long)INT_MAX) return LSSP_AMD_EUNSUPPORTED;
+    LSSP_HIP(B.get(&Gj, (size_t)ng));
+    k_bilu_graph<<<bilu_grid((long)nb + 1), 256, 0, c->stream>>>(nb, bs, A->Ap, A->Aj, Gp, Gj, cnt, flag + 1);
+    LSSP_HIP(hipGetLastError());
+    LSSP_TRY(mark("block graph"));
+    // 3. the symbolic ILU(level) of the block graph (level 0: the graph itself), 4. its level lists
+    BlockSymbolic sym{c};
+    const std::function<int(const char *)> sub = [&](const char *phase) {
+        return mark(strcmp(phase, "check") ? phase : "graph check");
+    };
+    LSSP_TRY(iluk_symbolic_dev(c, nb, ng, Gp, Gj, level, &sym.rp, sub));
+    RefactorPlan &rp = *sym.rp;
+    const long nblk = rp.nnz;
+    if (nblk < nb || nblk * bs2 + n > (long)INT_MAX) return LSSP_AMD_EUNSUPPORTED;  // L, U keep 32-bit row pointers
+    LSSP_TRY(iluk_split_pattern_dev(c, nb, rp, &sym.S));
+    LSSP_TRY(iluk_plan_levels_dev(c, nb, rp, sym.S));
+    // the plan lssp_amd_bilu_refactor works on: the symbolic pass's arrays are its pattern (the
+    // origin byte is the graph byte, the diagonal block is the first non-lower one)
+    BiluPlan *pp = new BiluPlan();
+    M->brf = pp;  // the handle's from here on: freed with it on every failure
+    BiluPlan &p = *pp;
+    p.nb = nb;
+    p.bs = bs;
+    p.nblk = nblk;
+    p.d_Bp = rp.d_Fp, p.d_Bj = rp.d_Fj, p.d_in = rp.d_fin, p.d_first = rp.d_dpos, p.d_rows = rp.d_rows;
+    rp.d_Fp = rp.d_Fj = rp.d_dpos = rp.d_rows = nullptr;
+    rp.d_fin = nullptr;
+    p.lev_off = std::move(rp.lev_off);
+    LSSP_HIP(hipMalloc(&p.d_Brow, sizeof(int) * (size_t)nblk));
+    LSSP_HIP(hipMalloc(&p.d_hit, (size_t)nblk));
+    LSSP_HIP(hipMalloc(&p.d_Bx, sizeof(double) * (size_t)nblk * bs2));
+    LSSP_HIP(hipMalloc(&p.d_Fx, sizeof(double) * (size_t)nblk * bs2));
+    LSSP_HIP(hipMalloc(&p.d_inv, sizeof(double) * (size_t)nb * bs2));
+    LSSP_HIP(hipMalloc(&p.d_flag, sizeof(int) * 2));
+    int *cl = nullptr, *cu = nullptr, *bl = nullptr, *bu = nullptr;
+    LSSP_HIP(B.get(&cl, (size_t)nb + 1));
+    LSSP_HIP(B.get(&cu, (size_t)nb + 1));
+    LSSP_HIP(B.get(&bl, (size_t)nb + 1));
+    LSSP_HIP(B.get(&bu, (size_t)nb + 1));
+    k_bilu_sides<<<bilu_grid((long)nb + 1), 256, 0, c->stream>>>(nb, p.d_Bp, p.d_Bj, p.d_first, p.d_Brow, cl, cu);
+    LSSP_HIP(hipGetLastError());
+    LSSP_TRY(mark("levels"));
+    // 5. the refactor's own kernels and launches (no graph compare: the pattern was just built from A)
+    LSSP_HIP(hipMemsetAsync(p.d_Bx, 0, sizeof(double) * (size_t)nblk * bs2, c->stream));
+    LSSP_HIP(hipMemsetAsync(p.d_hit, 0, (size_t)nblk, c->stream));
+    LSSP_HIP(hipMemsetAsync(p.d_flag, 0, sizeof(int) * 2, c->stream));
+    k_bilu_scatter<<<bilu_grid(n), 256, 0, c->stream>>>(n, bs, nnz, A->Ap, A->Aj, A->Ax, p.d_Bp, p.d_Bj, p.d_Bx,
+                                                       p.d_hit, p.d_flag);
+    LSSP_HIP(hipGetLastError());
+    LSSP_TRY(mark("scatter"));
+    bilu0_launch_levels(c, bs, p.lev_off, p.d_rows, p.d_Bp, p.d_Bj, p.d_Bx, p.d_inv, p.d_flag + 1);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipMemcpyAsync(h, p.d_flag, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    if (h[0]) return LSSP_AMD_EHIP;    // an entry of A outside the pattern made from A
+    if (h[1]) return LSSP_AMD_EINVAL;  // singular diagonal block
+    LSSP_TRY(mark("numeric BILU(0)"));
+    LSSP_TRY(bilu_commit_launch(c, p));
+    LSSP_TRY(mark("U scaling"));
+    // 6. the point factors: the rows' places from one scan a side, then the fill
+    LSSP_TRY(bilu_scan_excl(c, B, cl, bl, (size_t)nb + 1));
+    LSSP_TRY(bilu_scan_excl(c, B, cu, bu, (size_t)nb + 1));
+    LSSP_HIP(hipMemcpyAsync(h, bl + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipMemcpyAsync(h + 1, bu + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    if (h[0] < 0 || h[1] < 0 || (long)h[0] + h[1] + nb != nblk) return LSSP_AMD_EHIP;
+    F->nnzL = (int)((long)h[0] * bs2 + n);
+    F->nnzU = (int)((long)h[1] * bs2 + n);
+    LSSP_HIP(hipMalloc(&F->Lp, sizeof(int) * ((size_t)n + 1)));
+    LSSP_HIP(hipMalloc(&F->Up, sizeof(int) * ((size_t)n + 1)));
+    LSSP_HIP(hipMalloc(&F->Lj, sizeof(int) * (size_t)F->nnzL));
+    LSSP_HIP(hipMalloc(&F->Lx, sizeof(double) * (size_t)F->nnzL));
+    LSSP_HIP(hipMalloc(&F->Uj, sizeof(int) * (size_t)F->nnzU));
+    LSSP_HIP(hipMalloc(&F->Ux, sizeof(double) * (size_t)F->nnzU));
+    const unsigned eg = (unsigned)std::max<long>(1, std::min<long>(((long)nb + 3) / 4, 1L << 20));
+    k_bilu_expand<<<eg, 256, 0, c->stream>>>(nb, bs, false, p.d_Bp, p.d_Bj, p.d_first, bl, p.d_Fx, F->Lp, F->Lj, F->Lx);
+    k_bilu_expand<<<eg, 256, 0, c->stream>>>(nb, bs, true, p.d_Bp, p.d_Bj, p.d_first, bu, p.d_Fx, F->Up, F->Uj, F->Ux);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(c->stream));  // the scans' outputs are freed on return
+    return mark("expansion");
 }
 
 }  // namespace lssp_amd

@@ -383,7 +383,7 @@ const char *lssp_amd_strerror(int s)
     }
 }
 
-int lssp_amd_version(void) { return 11000; }
+int lssp_amd_version(void) { return 11100; }
 
 int lssp_amd_ctx_create(int device, lssp_amd_ctx **out)
 {

@@ -772,6 +772,57 @@ int lssp_amd_bilu_create(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, c
     }
 }
 
+// lssp_amd_bilu_create for a matrix in HBM: bilu_create_device
+// (bilu_factor.hip) leaves the plan lssp_amd_bilu_refactor works on and the point
+// factors L and U in HBM; both packet schedules come from the device builder,
+// and the factors are freed once the schedules stand -- the host copies, block
+// pattern included, are made from the plan by their first reader
+// (bilu_refactor_host_factors).  What the device builder refuses takes the host
+// copies and ilu_upload, as in iluk_general_create_dev; such a handle keeps no
+// plan: lssp_amd_bilu_refactor refuses it as it refuses the host-made one.
+static int bilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int level, int bs, lssp_amd_ilu **out)
+{
+    const int n = A->nrows;
+    LSSP_HIP(hipSetDevice(c->device));
+    PhaseClock clk(c, "bilu_create_dev");
+    return create_handle(c, n, 0, level, 0, clk, out, [&](lssp_amd_ilu *M) -> int {
+        SplitScratch S{c};
+        M->bs = bs;
+        LSSP_TRY(bilu_create_device(c, M, A, level, bs, &S.F, clk));
+        const size_t ninv = (size_t)n * bs;  // nb blocks of bs^2
+        LSSP_HIP(hipMalloc(&M->d_Dinv, sizeof(double) * ninv));
+        LSSP_HIP(hipMemcpyAsync(M->d_Dinv, M->brf->d_inv, sizeof(double) * ninv, hipMemcpyDeviceToDevice, c->stream));
+        const int st = device_schedules(c, M, S.F, clk);
+        if (st == LSSP_AMD_OK) {  // the middle stage's output, as ilu_upload gives a BILUK handle
+            LSSP_HIP(hipMalloc(&M->d_mid, sizeof(double) * std::max(n, 1)));
+            return LSSP_AMD_OK;
+        }
+        if (st != LSSP_AMD_EUNSUPPORTED) return st;
+        iluk_split_free(&S.F);  // the host copies come from the plan
+        LSSP_TRY(refactor_host_factors(M));
+        LSSP_TRY(clk.mark("download"));
+        (void)hipFree(M->d_Dinv);  // ilu_upload uploads the host copy
+        M->d_Dinv = nullptr;
+        bilu_plan_free(M->brf);
+        M->brf = nullptr;
+        return host_schedules(c, M, clk);
+    });
+}
+
+int lssp_amd_bilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int level, int bs, lssp_amd_ilu **out)
+{
+    LSSP_TRY(check_create_dev_args(c, A, false, 0, out));
+    if (bs < 1 || bs > BILU_MAX_BS || A->nrows % bs != 0) return LSSP_AMD_EINVAL;
+    if (level < 0) level = 1;  // pc.cxx: the reference's default iluk_level
+    // the device numeric path, one rank, levels that travel as bytes (iluk_symbolic_dev)
+    if (bs > BILU_MAX_BS_DEV || !one_block_local(A, 0) || level > 254) return LSSP_AMD_EUNSUPPORTED;
+    try {
+        return bilu_create_dev(c, A, level, bs, out);
+    } catch (const std::exception &) {
+        return LSSP_AMD_ENOMEM;
+    }
+}
+
 // New values on the same block pattern: scatter, graph compare, k_bilu0_level
 // over the kept level lists, U scaling, both record streams refilled
 // (bilu_factor.hip bilu_refactor_device); packet schedules, shadows and claim
@@ -779,8 +830,9 @@ int lssp_amd_bilu_create(lssp_amd_ctx *c, int n, const int *Ap, const int *Aj, c
 int lssp_amd_bilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A)
 {
     if (!c || !M || !A) return LSSP_AMD_EINVAL;
-    const bool eligible = M->bs >= 1 && M->bs <= BILU_MAX_BS_DEV && !M->bBp.empty() && M->line.ntiles == 0 &&
-                          M->lower.pk6_n > 0 && M->upper.pk6_n > 0 && M->d_Dinv;
+    // (a handle lssp_amd_bilu_create_dev made has its plan, and its host pattern only once something read it)
+    const bool eligible = M->bs >= 1 && M->bs <= BILU_MAX_BS_DEV && (M->brf || !M->bBp.empty()) &&
+                          M->line.ntiles == 0 && M->lower.pk6_n > 0 && M->upper.pk6_n > 0 && M->d_Dinv;
     if (!eligible || A->dist) return LSSP_AMD_EUNSUPPORTED;
     if (A->nrows != M->n || A->ncols != M->n) return LSSP_AMD_EINVAL;
     try {

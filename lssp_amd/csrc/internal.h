@@ -357,7 +357,9 @@ struct lssp_amd_ilu {
     // the creating matrix's block graph held it; the level is c_level
     std::vector<int> bBp, bBj;
     std::vector<unsigned char> bIn;
-    lssp_amd::BiluPlan *brf = nullptr;  // built by the first lssp_amd_bilu_refactor
+    // built by the first lssp_amd_bilu_refactor; a handle lssp_amd_bilu_create_dev made is born with it, and its
+    // bBp / bBj / bIn are downloaded from it with the other host copies (host_missing below)
+    lssp_amd::BiluPlan *brf = nullptr;
     // lssp_amd_ilu_create, ILUK with one block (lssp_amd_iluk_refactor's pattern
     // rule): per entry of the factor pattern F, 1 = an entry of the sorted
     // creating matrix, 0 = fill, 2 = an inserted diagonal (ilu_factor); empty:
@@ -586,6 +588,17 @@ int bilu_plan_build(lssp_amd_ctx *c, lssp_amd_ilu *M);
 void bilu_plan_free(BiluPlan *p);
 int bilu_refactor_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A);
 int bilu_refactor_host_factors(lssp_amd_ilu *M);
+// lssp_amd_bilu_create_dev (ilu_handle.cpp; bilu_factor.hip, bilu_create_dev.h), for a
+// single-rank square A with n % bs == 0, bs <= 8: M->brf = the plan lssp_amd_bilu_refactor works on, made
+// on the device -- rows check, block graph, iluk_symbolic_dev on the graph, its level lists,
+// k_bilu_scatter / k_bilu0_level / k_bilu_commit -- and *F = the point factors L and U expanded from the
+// committed blocks, in HBM, for the device schedule builder (the caller frees them: iluk_split_free, also
+// after a failure).  EUNSUPPORTED: a row whose columns do not ascend strictly inside [0, n), a block row
+// without its diagonal block, iluk_symbolic_dev's refusals, bs^2 * blocks + n beyond INT_MAX; EINVAL: a
+// singular diagonal block; ETIMEOUT: a bounded wait expired.  mark(phase) is called after each stage.
+struct IlutDevFactors;
+int bilu_create_device(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *A, int level, int bs, IlutDevFactors *F,
+                       const std::function<int(const char *)> &mark);
 // trisolve.hip: the V array of every packet record of t rewritten from the
 // committed block values Fx (k_pk6_refill); C, D, ROW and everything else stay
 int launch_pk6_refill(lssp_amd_ctx *c, const TriSched &t, bool upper, int bs, int nb, const int *Bp, const int *Bj,

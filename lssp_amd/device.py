@@ -454,6 +454,22 @@ class DILU:
         return cls(dev, h)
 
     @classmethod
+    def bilu_create_dev(cls, dev: Device, A: DMat, bs: int, level: int = 0):
+        """bilu() for a matrix that lives in HBM (lssp_amd_bilu_create_dev), bs <= 8: block graph,
+        symbolic block ILU(level), numeric factorization, expansion to L and U and both packet
+        schedules (schedule(w)["origin"] == 1) are made on the device, bitwise bilu()'s handle.
+        A's arrays stay in HBM and A may be closed on return; factors() / diag() download on first
+        use; bilu_refactor() is eligible at once and builds nothing.  Rows must be column-sorted
+        and every block row must hold its diagonal block.  bs 9..32, a distributed A, an unsorted
+        row, a repeated column, a block row without its diagonal block, a working block row
+        beyond ilut_capacity() blocks on a side and level > 254 raise LsspError with status 6
+        (unsupported) and leave A as it was: use bilu() there.  A singular diagonal block, n not
+        a multiple of bs and a non-square A raise status 1."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_bilu_create_dev(dev.h, A.h, level, bs, ctypes.byref(h)), "bilu_create_dev")
+        return cls(dev, h)
+
+    @classmethod
     def from_ldu(cls, dev: Device, L, D, U):
         """BILUK factors as the reference leaves them in pc.L / pc.D / pc.U (D: block diagonal CSR)"""
         Lp, Lj, Lx = _i32(L[0]), _i32(L[1]), _f64(L[2])
