@@ -375,6 +375,7 @@ struct SpmvArgs {
     const unsigned long long *val;
     const int *voff;
     int nval, v8;
+    int uni;  // COL_VAL: a wave of 64 equal rows resolves the row length once (spmv_uniform)
 };
 
 // The 256-row blocks are dealt so that each of the 8 XCDs owns one contiguous
@@ -407,13 +408,51 @@ struct SpmvArgs {
 // copy: the codes and dot operands of all of them are loaded up front, then
 // all their x gathers are issued, then each block runs its own epilogue and
 // writes its own rows and chunk partial, as a workgroup of its own would.
+// Uniform waves (LSSP_AMD_SPMV_UNI): on a structured grid most waves hold 64
+// rows with one code (216^3: 2/3 of them), so the row's length is the same in
+// every lane.  A wave whose 64 code bytes of a live block are equal and whose
+// rows all lie below nrows takes the length as a scalar (readfirstlane of the
+// LDS word) and resolves it once per block, by a uniform switch: its products
+// are a straight multiply-add chain of exactly that length, with no compare and
+// select per entry (7-entry rows: 14 vector instructions for 36).  Offsets and
+// values it still reads per lane from the LDS table: taking them as scalars too
+// (scalar loads from the global table, gathers from a scalar base) issued a
+// third of the instructions and measured slower -- DESIGN 6.0b.  Same entries,
+// same order, each product rounded on its own: the bits of the per-lane path,
+// which every other wave of the workgroup still takes.
+// LSSP_AMD_SPMV_WAVES: the waves per SIMD the register allocation aims at.  5
+// holds every COL_VAL instance to 96 VGPRs (the three-dot one had 106 and ran
+// 4 waves).  The attribute sits on the whole template and is a lower bound
+// only: it caps the registers at what five waves allow and raises nothing, so
+// the other modes' instances (under 48 VGPRs: 6 to 8 waves) compile as before.
 enum { COL_J = 0, COL_ID = 1, COL_ROW = 2, COL_VAL = 3 };
 #ifndef LSSP_AMD_SPMV_VB
 #define LSSP_AMD_SPMV_VB 4
 #endif
+#ifndef LSSP_AMD_SPMV_UNI
+#define LSSP_AMD_SPMV_UNI 1
+#endif
+#ifndef LSSP_AMD_SPMV_WAVES
+#define LSSP_AMD_SPMV_WAVES 5
+#endif
 constexpr int SPMV_VB = LSSP_AMD_SPMV_VB;
+constexpr bool SPMV_UNI = LSSP_AMD_SPMV_UNI != 0;
+// a uniform wave's row of L entries: the products added in CSR order onto +0.0,
+// the values read per lane from the LDS table (sv[u][c])
+template <int L>
+__device__ __forceinline__ double uni_row(const double (&xv)[8], const double (*sv)[ROWVAL_MAX], unsigned c)
+{
+    double s = 0;
+#pragma unroll
+    for (int u = 0; u < L; u++) s += xv[u] * sv[u][c];
+    return s;
+}
 template <int EPI, int NRED, int CM>
-__global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
+__global__ __launch_bounds__(256)
+#if LSSP_AMD_SPMV_WAVES > 0
+__attribute__((amdgpu_waves_per_eu(LSSP_AMD_SPMV_WAVES)))
+#endif
+void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
 {
     constexpr bool CMP = CM == COL_ID, ROW = CM == COL_ROW, VAL = CM == COL_VAL;
     static_assert(256 * 8 <= SPMV_CAP, "a row-coded block fits the staging buffer");
@@ -471,23 +510,37 @@ __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_p
             if (q < ROWPAT_LEN) sval[q][c] = __longlong_as_double((long long)a.val[a.nval + t]);
         }
         if (gv != 0.0) return;
+        int len[SPMV_VB];
+        double xv[SPMV_VB][8];
+        // which of the wave's blocks are uniform: 64 equal codes, all rows in the matrix
+        bool uni[SPMV_VB];
+        int ulen[SPMV_VB];  // (kept apart from len: a scalar)
+        const int wrow = __builtin_amdgcn_readfirstlane(tid & ~63);
+#pragma unroll
+        for (int j = 0; j < SPMV_VB; j++) {
+            uni[j] = false;
+            ulen[j] = 0;
+            if (SPMV_UNI && NRED > 0 && a.uni) {  // (the plain product measured slower with it: DESIGN 6.0b)
+                const unsigned c0 = __builtin_amdgcn_readfirstlane(code[j]);
+                const int rw = (int)(blk[j] * 256) + wrow;  // the wave's first row
+                uni[j] = live[j] && rw + 63 < a.nrows && __ballot(code[j] != c0) == 0;
+            }
+        }
         __syncthreads();
         // every x gather of every block is issued before the first product, with no
         // branch on the row's length around them: the table repeats a row's last
         // offset past its length (an empty row's are 0 and read x[0]), a lane past
         // the matrix's last row gathers for that row, and entry 7 is skipped
         // unless some row of the matrix has 8 entries
-        int len[SPMV_VB];
-        double xv[SPMV_VB][8];
 #pragma unroll
         for (int j = 0; j < SPMV_VB; j++) {
             const int r = (int)(blk[j] * 256) + tid;
             const int lt = svoff[ROWPAT_LEN][code[j]];
             const double *xb = a.x + (lt > 0 ? min(r, a.nrows - 1) : 0);
             len[j] = r < a.nrows && live[j] ? lt : 0;
+            if (uni[j]) ulen[j] = __builtin_amdgcn_readfirstlane(lt);
 #pragma unroll
             for (int u = 0; u < 8; u++) {
-                xv[j][u] = 0.0;
                 if (u == 7 && !a.v8) continue;
                 xv[j][u] = xb[svoff[u][code[j]]];
             }
@@ -498,6 +551,22 @@ __global__ __launch_bounds__(256) void k_spmv3(SpmvArgs a, long nblk, long nnz_p
 #pragma unroll
         for (int j = 0; j < SPMV_VB; j++) {
             sum[j] = 0;
+            if (uni[j]) {
+                // the length resolved once per block: entries past it are not added, which
+                // is adding +0.0 (a wave of empty rows: no product, +0.0)
+                switch (ulen[j]) {
+                case 1: sum[j] = uni_row<1>(xv[j], sval, code[j]); break;
+                case 2: sum[j] = uni_row<2>(xv[j], sval, code[j]); break;
+                case 3: sum[j] = uni_row<3>(xv[j], sval, code[j]); break;
+                case 4: sum[j] = uni_row<4>(xv[j], sval, code[j]); break;
+                case 5: sum[j] = uni_row<5>(xv[j], sval, code[j]); break;
+                case 6: sum[j] = uni_row<6>(xv[j], sval, code[j]); break;
+                case 7: sum[j] = uni_row<7>(xv[j], sval, code[j]); break;
+                case 8: sum[j] = uni_row<8>(xv[j], sval, code[j]); break;  // (some row has 8 entries: a.v8)
+                default: break;
+                }
+                continue;
+            }
 #pragma unroll
             for (int u = 0; u < 8; u++) {
                 if (u == 7 && !a.v8) continue;
@@ -948,6 +1017,17 @@ static int spmv_valcode()
     }();
     return k;
 }
+// LSSP_AMD_SPMV_UNIFORM=0: every wave of a value-coded product takes the
+// per-lane path (tests, A/B runs); the same kernel, so tune_spmv_streams times
+// what runs
+static int spmv_uniform()
+{
+    static const int k = [] {
+        const char *e = getenv("LSSP_AMD_SPMV_UNIFORM");
+        return e ? atoi(e) : 1;
+    }();
+    return k;
+}
 static int spmv_streams(const lssp_amd_mat *A)
 {
     const int e = spmv_streams_env();
@@ -991,7 +1071,7 @@ int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, c
     if (nb == 0) return LSSP_AMD_OK;
     SpmvArgs a{A->nrows, A->Ap, A->Aj, A->Ax, x, y, z, alpha, beta, w0, w1, c->d_part, c->part_cap,
                A->Ad, A->d_off, A->ndiag, c->guard, cb, spmv_streams(A), 0, 0, 0, spmv_ntv(),
-               nullptr, nullptr, 0, {0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, nullptr, 0, 0};
+               nullptr, nullptr, 0, {0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, nullptr, 0, 0, 0};
     if (A->npat > 0 && spmv_rowcode()) {
         a.Ac = A->Ac;
         a.pat = A->d_pat;
@@ -1003,6 +1083,7 @@ int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, c
             a.voff = A->d_voff;
             a.nval = A->nval;
             a.v8 = A->val_thr[7] < A->nval;
+            a.uni = spmv_uniform() != 0;
         }
     }
     const long plane = A->max_off_int;
