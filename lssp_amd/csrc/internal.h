@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -221,12 +222,14 @@ struct TriSched {
     int bp_unit = 0, bp_origin = 0;
 };
 
-// ---- line sweeps of structured ILU(0) factors (linesweep.hip) ----------------
-// A tile is 256 / P lines x P planes = 256 rows per step, P in {4, 8, 16}
-// (chosen per factor, build_line_sweep): a compute wave's 64 lanes are P / 4
-// groups of 256 / P lines, each lane holds 2 planes, 2 compute waves.  Squarer
-// tiles = fewer tile-to-tile hand-offs on a sweep's critical path (216^3: 56
-// hops with 64 x 4 tiles, 26 with 16 x 16).
+// ---- line sweeps of structured factors (linesweep.hip, linefill.hip) ---------
+// The 5-/7-point ILU(0) (kind 0, k_line2) and the 7-point ILU(1) pattern (kind
+// 1, k_linef) run on tiles of NJ = 16 lines x P = 8 planes, LV = 2 levels per
+// workgroup step: two compute waves, wave w owns planes 4w .. 4w+3 and runs
+// one level later per w, a lane one row per level.  Kind 1's lines are the
+// skewed j' = j + k.  Tile (J, K) of the W x S tiles takes its inputs from
+// tiles (J-1, K) and (J, K-1) through hand-off buffers in HBM; a small 2-D
+// grid of either kind runs on one workgroup instead (k_lineg, g2).
 enum { LT_KIN = 1, LT_JIN = 2, LT_KOUT = 4, LT_JOUT = 8, LT_SKIP = 16 };  // LT_SKIP: k_linef tile wholly off the grid
 struct LineGeom {
     int nx = 0, ny = 0, nz = 0;
@@ -236,30 +239,31 @@ struct LineGeom {
 struct LineTile {  // one workgroup's unit of work, in its sweep's coordinates
     int j0, nj, k0, np;
     int flags;        // LT_*
-    int T;            // levels (k_line2: padded to a whole number of two-level steps)
-    int roff;         // (unused)
-    int tk, tj;       // producer tiles of the k / j inputs (-1: none)
+    int T;            // levels (padded to a whole number of LV-level steps)
+    int tk, tj;      // producer tiles of the k / j inputs (-1: none)
     int ut;           // L sweep: the mirror U tile (its rhs stream)
     long long cbase;  // first row of the tile in its sweep's streams
     long long ubase;  // L sweep: cbase of the mirror U tile
 };
 struct LineSweep {
-    int nx = 0, ny = 0, nz = 0, ntiles = 0, tmax = 0, NA = 3;
-    int P = 4;    // planes per tile
-    int NJ = 64;  // lines per tile (k_line2: 16)
-    int LV = 1;   // levels per workgroup step (k_line2: 2; its planes P/2.. run one level later)
-    long rows_total = 0;
+    int nx = 0, ny = 0, nz = 0, ntiles = 0, tmax = 0;
+    int NA = 3;   // coefficients per row (kind 0: 3, + the diagonal 4; kind 1: 6, 7)
+    int P = 8;    // planes per tile
+    int NJ = 16;  // lines per tile
+    int LV = 2;   // levels per workgroup step
+    long rows_total = 0;  // stream rows: per tile T levels x P planes x nj lines
     LineTile *d_tiles = nullptr;
     double *d_coef = nullptr;
     unsigned long long *d_claim = nullptr;
-    int *d_order = nullptr;  // k_line2: the tile of each claim (anti-diagonal order)
+    int *d_order = nullptr;  // the tile of each claim: producers before consumers (line_layout)
     mutable unsigned long long base = 0;
     std::vector<LineTile> h_tiles;
 };
 struct LineILU {
     LineGeom g;
-    int P = 4, NJ = 64, LV = 1, W = 0, S = 0, tmax = 0, ntiles = 0;
-    int kind = 0;  // 0: 7-point ILU(0) (linesweep.hip); 1: 7-point ILU(1) pattern (linefill.hip)
+    int P = 8, NJ = 16, LV = 2;  // the tiles' (k_lineg: 1 plane, ny lines, 1 level)
+    int W = 0, S = 0, tmax = 0, ntiles = 0;  // W x S tiles (ntiles > 0: line sweeps active)
+    int kind = 0;  // 0: 5-/7-point ILU(0) (linesweep.hip); 1: 7-point ILU(1) pattern (linefill.hip)
     LineSweep L, U;
     double *d_ustream = nullptr;  // the U sweep's rhs, written by the L sweep
     double *d_lstream = nullptr;  // the L sweep's rhs in its stream layout (k_line_rhs)
@@ -638,8 +642,42 @@ int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std
 bool line_enabled();  // linesweep.hip: LSSP_AMD_LINE=0 turns every line sweep off
 bool linefill_box_tiled(int nx, int ny, int nz);
 int build_linefill_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li);
-int launch_linefill_apply(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs);
+// What the two tiled builds share (linesweep.hip).  line_layout, from a sweep's
+// tiles (ls.P / NJ / LV set; W tiles per tile row): every tile's place in the
+// streams, the tile table, the claim counter, the coefficient stream's
+// allocation (line_coef_len doubles; its values per kind) and the claim order
+// -- tile (J, K) by ascending wj J + wk K, its earliest start, so both producers
+// of a tile are claimed before it.  finish_line_tiles, after both layouts: the
+// L tiles' links to their mirror U tiles, both rhs streams (zeroed), the
+// hand-off buffers (hk_stride / hj_stride doubles per tile, armed), and the
+// final synchronise.
+size_t line_coef_len(const LineSweep &ls);
+int line_layout(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, int NA, int W, int wj, int wk,
+                LineSweep &ls);
+int finish_line_tiles(lssp_amd_ctx *c, LineILU &li, long hk_stride, long hj_stride);
+// line_args: the kernel arguments (linesweep_dev.h) of one sweep of li (which: 0
+// L, 1 U) from its rhs stream; outk 2: out = the U rhs stream, 1: natural order
+// (tail: the product run by the sweep's workgroups after its tiles, outk 1
+// only).  line_launch: that sweep on one of a call site's two kernels -- kern
+// (lds0 bytes of LDS), or, with a.tail, the tail instantiation kernt (ldst) --
+// with min(tiles, CUs) workgroups of block threads; sets a kernel's dynamic LDS
+// limit at its first launch and advances the sweep's claim base by the claims
+// the launch consumes.
+struct LineArgs;
 struct LineTail;
+struct LineKernels {  // one static object per call site
+    void (*kern)(LineArgs), (*kernt)(LineArgs);
+    int lds0, ldst, block;
+    std::atomic<bool> sized[2] = {};  // kern's / kernt's LDS limit is set
+};
+LineArgs line_args(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
+                   const LineTail *tail);
+int line_launch(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &a, LineKernels &k);
+// k_linef's rhs gather and sweep launch (linefill.hip; launch_line_apply / _sweep /
+// _apply_spmv run them for kind 1): arguments as linesweep.hip's launch_line_gather / launch_line2
+int launch_linef_gather(lssp_amd_ctx *c, const LineSweep &ls, int mirror, const double *rhs, double *stream);
+int launch_linef(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
+                 const LineTail *tail = nullptr);
 // small 2-D grids on one workgroup (linefill.hip): cl / cu hold the L / U rows in
 // sweep order, components S, (SE,) W (, diag); mode 0 apply, 1 L, 2 U
 int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const std::vector<double> &cl,
@@ -652,10 +690,7 @@ inline bool lineg_fits(const LineGeom &g, int fill)
 {
     const long nyp = (g.ny + 63) / 64 * 64, V = g.nx + (fill ? 2L : 1L) * (g.ny - 1);
     return (long)g.nx * g.ny * 8 < (1L << 30) && V * 5 * nyp * 8 + 1024 < (1L << 30);
-}  // linesweep_dev.h
-int launch_linefill_apply_tail(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs, const LineTail &T,
-                               long *tail_waves);
-int launch_linefill_sweep(lssp_amd_ctx *c, const LineILU &li, int which, double *x, const double *rhs);
+}
 void free_line_sweep(LineILU &li);
 // lssp_amd_ilu_refactor (ilu_handle.cpp).  ilu_factor.hip: the plan from the host
 // copies of the factor pattern; *same = A's device pattern equals it; the

@@ -46,10 +46,12 @@
 // k-tile's line 0 BE operand of plane 0, which no other tile of that k-tile
 // reads.
 //
-// Roles and streams are k_line2's (linesweep.hip): 2 compute waves, NL LDS-DMA
-// loader waves (the step's coefficient blocks {B, BE, BN, S, SE, W(, diag)}
-// and rhs block D steps ahead), 1 poller (the hand-off inputs DH steps ahead),
-// SW storers (the U sweep's rhs stream or the natural-order output, re-arms).
+// The kernel arguments and the host's layout, launch and apply sequences are
+// shared with k_line2 (linesweep_dev.h, linesweep.hip).  The roles are
+// k_line2's in kind: 2 compute waves, NL LDS-DMA loader waves (the step's
+// coefficient blocks {B, BE, BN, S, SE, W(, diag)} and rhs block D steps
+// ahead), 1 poller (the hand-off inputs DH steps ahead), SW storers (the U
+// sweep's rhs stream or the natural-order output, re-arms).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -82,6 +84,7 @@ struct Slot {
     static constexpr int BYTES = JFIN + LV * P * 8;
     static_assert(KFIN % 16 == 0 && JFIN % 16 == 0 && BYTES % 16 == 0, "slot alignment");
 };
+constexpr int SC = -1;  // first computed step: levels -2, -1 prime S, B
 template <int OUT>
 constexpr int rsl() { return OUT == 1 ? 16 : 4; }
 template <int NA, int OUT, int D>
@@ -239,27 +242,14 @@ int fill_T(int nx, int nj, int np)
     return (T + lf::LV - 1) / lf::LV * lf::LV;
 }
 
-// src == nullptr: the coefficient stream is zeroed on the context's stream
-// (launch_linefill_refill writes it)
-int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, int W, const FillCoef *src,
-                int NA, LineSweep &ls)
+// the coefficient stream of a laid-out sweep (line_layout) from the host factors
+int fill_upload(const LineGeom &g, const FillCoef &src, LineSweep &ls)
 {
     using namespace lf;
-    const int nx = g.nx;
-    std::vector<LineTile> tt = tiles;
-    long rows_total = 0;
-    int tmax = 0;
-    for (LineTile &t : tt) {
-        t.roff = 0;
-        t.cbase = rows_total;
-        rows_total += (long)t.T * P * t.nj;
-        tmax = std::max(tmax, t.T);
-    }
-    const long slack = 16 * 1024 / 8;  // the loaders' whole 1 KB pieces past the last block
-    const size_t coef_n = (size_t)rows_total * NA + slack;
-    std::vector<double> coef;
-    if (src) coef.assign(coef_n, 0.0);
-    if (src) parallel_for((long)tt.size(), [&](long t0, long t1) {
+    const int nx = g.nx, NA = ls.NA;
+    const std::vector<LineTile> &tt = ls.h_tiles;
+    std::vector<double> coef(line_coef_len(ls), 0.0);
+    parallel_for((long)tt.size(), [&](long t0, long t1) {
         for (long ti = t0; ti < t1; ti++) {
             const LineTile &t = tt[ti];
             for (int p = 0; p < t.np; p++)
@@ -271,41 +261,12 @@ int fill_upload(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> 
                         const long v = i + off;
                         const long r = ((long)(t.k0 + p) * g.ny + j) * nx + i;
                         double *dst = coef.data() + (size_t)(t.cbase + v * P * t.nj + p * t.nj + l) * NA;
-                        for (int a = 0; a < NA; a++) dst[a] = src->c[(size_t)r * NA + a];
+                        for (int a = 0; a < NA; a++) dst[a] = src.c[(size_t)r * NA + a];
                     }
                 }
         }
     });
-    ls.nx = g.nx;
-    ls.ny = g.ny;
-    ls.nz = g.nz;
-    ls.ntiles = (int)tt.size();
-    ls.tmax = tmax;
-    ls.rows_total = rows_total;
-    ls.NA = NA;
-    ls.P = P;
-    ls.NJ = NJ;
-    ls.LV = LV;
-    LSSP_HIP(hipMalloc(&ls.d_tiles, sizeof(LineTile) * tt.size()));
-    LSSP_HIP(hipMemcpy(ls.d_tiles, tt.data(), sizeof(LineTile) * tt.size(), hipMemcpyHostToDevice));
-    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * coef_n));
-    if (src) LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef_n, hipMemcpyHostToDevice));
-    else LSSP_HIP(hipMemsetAsync(ls.d_coef, 0, sizeof(double) * coef_n, c->stream));
-    LSSP_HIP(hipMalloc(&ls.d_claim, sizeof(unsigned long long)));
-    LSSP_HIP(hipMemset(ls.d_claim, 0, sizeof(unsigned long long)));
-    // claims in order of the tile's earliest start: a j-hop costs ~2 nj + 4
-    // levels, a k-hop ~np + 1 + 4; both producers of a tile come before it
-    const int nt = (int)tt.size();
-    std::vector<int> ord(nt);
-    for (int q = 0; q < nt; q++) ord[q] = q;
-    std::stable_sort(ord.begin(), ord.end(), [W](int x, int y) {
-        const long kx = (long)(x % W) * (2 * NJ + 4) + (long)(x / W) * (P + 5);
-        const long ky = (long)(y % W) * (2 * NJ + 4) + (long)(y / W) * (P + 5);
-        return kx != ky ? kx < ky : x < y;
-    });
-    LSSP_HIP(hipMalloc(&ls.d_order, sizeof(int) * nt));
-    LSSP_HIP(hipMemcpy(ls.d_order, ord.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
-    ls.h_tiles = std::move(tt);
+    LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
     return LSSP_AMD_OK;
 }
 
@@ -442,39 +403,26 @@ static int build_linefill_tiles(lssp_amd_ctx *c, const LineGeom &g, const FillCo
     const int NAL = g.unitL ? 6 : 7;  // (unit L: its diagonal is not streamed)
     li.g = g;
     li.kind = 1;
-    li.P = P;
-    li.NJ = NJ;
-    li.LV = LV;
+    li.P = li.L.P = li.U.P = P;
+    li.NJ = li.L.NJ = li.U.NJ = NJ;
+    li.LV = li.L.LV = li.U.LV = LV;
     li.W = W;
     li.S = S;
-    LSSP_TRY(fill_upload(c, g, Lt, W, cl, NAL, li.L));
-    LSSP_TRY(fill_upload(c, g, Ut, W, cu, 7, li.U));
-    for (int K = 0; K < S; K++)
-        for (int J = 0; J < W; J++) {
-            LineTile &l = li.L.h_tiles[(size_t)K * W + J];
-            l.ut = (S - 1 - K) * W + (W - 1 - J);
-            l.ubase = li.U.h_tiles[l.ut].cbase;
-        }
-    LSSP_HIP(hipMemcpy(li.L.d_tiles, li.L.h_tiles.data(), sizeof(LineTile) * li.L.h_tiles.size(),
-                       hipMemcpyHostToDevice));
-    const long slack = 16 * 1024 / 8;
-    LSSP_HIP(hipMalloc(&li.d_ustream, sizeof(double) * (li.U.rows_total + slack)));
-    LSSP_HIP(hipMemset(li.d_ustream, 0, sizeof(double) * (li.U.rows_total + slack)));  // rows off the grid stay +0.0
-    LSSP_HIP(hipMalloc(&li.d_lstream, sizeof(double) * (li.L.rows_total + slack)));
-    LSSP_HIP(hipMemset(li.d_lstream, 0, sizeof(double) * (li.L.rows_total + slack)));
-    li.tmax = std::max(li.L.tmax, li.U.tmax);
-    // rows: every step the poller may address (steps up to TS + DH + 1, two rows each, + HJ0)
-    const long rows = li.tmax + 32;
-    li.hk_stride = rows * HKS;
-    li.hj_stride = rows * P;
-    li.ntiles = (int)Lt.size();
-    li.hk_n = li.hk_stride * li.ntiles;
-    li.hj_n = li.hj_stride * li.ntiles;
-    LSSP_HIP(hipMalloc(&li.d_hk, sizeof(double) * li.hk_n));
-    LSSP_HIP(hipMalloc(&li.d_hj, sizeof(double) * li.hj_n));
-    LSSP_TRY(line_rearm(c, li));
-    LSSP_HIP(hipStreamSynchronize(c->stream));
-    return LSSP_AMD_OK;
+    // claims in order of the tile's earliest start: a j-hop costs ~2 nj + 4
+    // levels, a k-hop ~np + 1 + 4
+    LSSP_TRY(line_layout(c, g, Lt, NAL, W, 2 * NJ + 4, P + 5, li.L));
+    LSSP_TRY(line_layout(c, g, Ut, 7, W, 2 * NJ + 4, P + 5, li.U));
+    if (cl && cu) {
+        LSSP_TRY(fill_upload(g, *cl, li.L));
+        LSSP_TRY(fill_upload(g, *cu, li.U));
+    } else {
+        LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * line_coef_len(li.L), c->stream));
+        LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * line_coef_len(li.U), c->stream));
+    }
+    // hand-off rows: every step the poller may address (steps up to TS + DH + 1,
+    // two rows each, + HJ0), HKS k entries and P j entries each
+    const long rows = std::max(li.L.tmax, li.U.tmax) + 32;
+    return finish_line_tiles(c, li, rows * HKS, rows * P);
 }
 
 int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
@@ -519,29 +467,10 @@ int build_linefill_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li)
 }
 
 // ---------------------------------------------------------------------------
-// device
+// device: k_linef (arguments: LineArgs, linesweep_dev.h)
 // ---------------------------------------------------------------------------
-struct FillArgs {
-    int nx, ny, ntiles;
-    long n;
-    const LineTile *tiles;
-    const double *coef;
-    const double *rhs;  // the sweep's rhs stream
-    double *out;        // OUT 1: natural-order output; OUT 2: the U rhs stream
-    double *hk, *hj;
-    long hk_stride, hj_stride;
-    unsigned long long *claim;
-    unsigned long long base;
-    const int *order;  // the tile of each claim
-    int mirror;        // U sweep: natural row = n-1 - sweep row
-    int *err;
-    const double *guard;  // lssp_amd_ctx::guard
-    int tail;     // OUT 1: run the product tl after the tiles (linesweep_dev.h LineTail)
-    LineTail tl;
-};
-
 template <int NA, int OUT, int NL, int D, int DH, int SW, bool TL = false>
-__global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
+__global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(LineArgs a)
 {
     // TL: the instantiation that can run the tail product (kept apart so the
     // plain sweep does not carry the product's registers; k_line2 alike)
@@ -552,14 +481,9 @@ __global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
     constexpr int LA = 2;  // the loaders complete step s+LA's slot during step s
     constexpr int R = D + 1;
     constexpr int RSL = rsl<OUT>();
-#ifndef LINEF_NITEM
-    constexpr int NITEM = SL::NPC + SL::NRP;
-#else
-    constexpr int NITEM = LINEF_NITEM;  // timing experiments only: a step's later DMA pieces are not loaded
-#endif
-    constexpr int KPER = (NITEM + NL - 1) / NL;
     constexpr int S0 = -2 * ((D + 2) / 2);  // first step of every role (even, <= -D-1)
-    constexpr int SC = -1;                  // first computed step: levels -2, -1 prime S, B
+    constexpr int NITEM = SL::NPC + SL::NRP;  // DMA instructions per step, shared by the loaders
+    constexpr int KPER = (NITEM + NL - 1) / NL;
     static_assert(DH >= 2 && DH < D && (D - LA) * KPER <= 63 && 2 * (DH - 1) <= 63, "leads");
     static_assert(OUT == 1 || OUT == 2, "out");
     static_assert(NA == 6 || NA == 7, "coefficients");
@@ -766,11 +690,11 @@ __global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
         } else if (wave == 2 + NL) {
             // ---------------- poller ----------------
             // At step s: LDS-DMA sc1 reads of step s+DH's k rows (hk rows 2q+2,
-            // 2q+3: 2 x 18 entries, lanes 0..17 x 16 B) and step s+DH+1's j rows
-            // (hj q = 2q+1, 2q+2: 2 x 8 entries, lanes 0..7); then the k-inputs of
-            // step s+1 and the j-inputs of step s+2 are waited for and checked
-            // (the compute reads the j-inputs one step ahead).  A tile without a
-            // k (j) input gets +0.0 there.
+            // 2q+3: 2 x 18 entries, lanes 0..17 x 16 B) and j rows (hj q = 2q+1,
+            // 2q+2: 2 x 8 entries, lanes 0..7); then the k- and j-inputs of step
+            // s+1 (issued DH-1 steps ago) are waited for and checked: the compute
+            // reads both at the start of their own step.  A tile without a k (j)
+            // input gets +0.0 there.
             const double *hk = a.hk + (long)max(d.tk, 0) * a.hk_stride;
             const double *hj = a.hj + (long)max(d.tj, 0) * a.hj_stride;
             const int kmax = (int)(a.hk_stride / HKS) - 2, jmax = (int)(a.hj_stride / P) - 2;  // first rows of a pair
@@ -902,7 +826,7 @@ __global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
                 constexpr int PS = LV * ROWS / 64 / SW;
                 static_assert(LV * ROWS % (64 * SW) == 0, "chunks");
                 double *po[PS];
-                int vlo[PS], lvs[PS], roff[PS];
+                int vlo[PS], lvs[PS], rix[PS];
 #pragma unroll
                 for (int u = 0; u < PS; u++) {
                     const int k = (w + u * SW) * 64 + lane;
@@ -910,7 +834,7 @@ __global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
                     const int pp = min(p, np - 1), lq = min(l, nj - 1);
                     const int j = d.j0 + l - d.k0 - p;
                     lvs[u] = lv;
-                    roff[u] = p * NJ + l;
+                    rix[u] = p * NJ + l;
                     vlo[u] = p < np && l < nj && (unsigned)j < (unsigned)a.ny ? 2 * l + p + sig(p) : 1 << 30;
                     const long Cp = (long)nx - 1 + 2 * (nj - 1) + np - 1 + sig(pp) + sig(np - 1 - pp);
                     po[u] = a.out + d.ubase + Cp * SB + (long)(np - 1 - pp) * nj + (nj - 1 - lq);
@@ -921,7 +845,7 @@ __global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
 #pragma unroll
                         for (int u = 0; u < PS; u++) {
                             const int v = LV * q + lvs[u];
-                            const double x = res[(v & (RSL - 1)) * ROWS + roff[u]];
+                            const double x = res[(v & (RSL - 1)) * ROWS + rix[u]];
                             if ((unsigned)(v - vlo[u]) < (unsigned)nx) po[u][-SB * v] = x;
                         }
                     }
@@ -933,7 +857,7 @@ __global__ __launch_bounds__(64 * lf::waves(NL, SW)) void k_linef(FillArgs a)
     }
     if constexpr (TL) {
         if (a.tail) {  // no tile left for this workgroup: its waves run the tail product
-            int *soff = reinterpret_cast<int *>(smem);  // (the ring's LDS is free now; linef_launch_t reserves TAIL_LDS_BYTES)
+            int *soff = reinterpret_cast<int *>(smem);  // (the ring's LDS is free now; line_tail_lds reserves it)
             __syncthreads();
             if (threadIdx.x < a.tl.ndiag) soff[threadIdx.x] = a.tl.off[threadIdx.x];
             __syncthreads();
@@ -1161,7 +1085,6 @@ int launch_lineg(lssp_amd_ctx *c, const LineILU &li, int mode, double *x, const 
     return LSSP_AMD_OK;
 }
 
-namespace {
 #ifndef LINEF_D
 #define LINEF_D 6  // loader lead (steps of two levels)
 #endif
@@ -1172,9 +1095,11 @@ namespace {
 // loaders; profiles/r04/r04k_linef_variants_128.txt)
 #define LINEF_DH 2
 #endif
+namespace {
 constexpr int LF_NL = 4, LF_SW = 4;
+}
 
-int linef_gather(lssp_amd_ctx *c, const LineSweep &ls, int mirror, const double *rhs, double *stream)
+int launch_linef_gather(lssp_amd_ctx *c, const LineSweep &ls, int mirror, const double *rhs, double *stream)
 {
     const int nq = (ls.tmax + LF_RUN - 1) / LF_RUN;
     const long grid = (long)ls.ntiles * nq;
@@ -1184,80 +1109,27 @@ int linef_gather(lssp_amd_ctx *c, const LineSweep &ls, int mirror, const double 
     return LSSP_AMD_OK;
 }
 
+namespace {
 template <int NA, int OUT>
-int linef_launch_t(lssp_amd_ctx *c, const LineSweep &ls, const FillArgs &a)
+int linef_launch_t(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &a)
 {
-    // (a sweep with natural-order output and the tail product reserves what the product needs)
-    constexpr int lds0 = lf::lds_bytes<NA, OUT, LINEF_D>();
-    constexpr int ldst = OUT == 1 && lds0 < TAIL_LDS_BYTES(0) ? TAIL_LDS_BYTES(0) : lds0;
+    constexpr int lds0 = lf::lds_bytes<NA, OUT, LINEF_D>(), ldst = OUT == 1 ? line_tail_lds(lds0) : lds0;
     static_assert(ldst <= 160 * 1024, "LDS");
-    const int lds = a.tail ? ldst : lds0;
     static_assert(OUT != 1 || lf::waves(LF_NL, LF_SW) >= TAIL_WAVES, "the tail product's roles");
-    auto kern = k_linef<NA, OUT, LF_NL, LINEF_D, LINEF_DH, LF_SW>;
-    auto kernt = k_linef<NA, OUT, LF_NL, LINEF_D, LINEF_DH, LF_SW, OUT == 1>;
-    static bool attr = false;
-    if (!attr) {
-        LSSP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds0));
-        LSSP_HIP(hipFuncSetAttribute((const void *)kernt, hipFuncAttributeMaxDynamicSharedMemorySize, ldst));
-        attr = true;
-    }
-    const int grid = std::min(ls.ntiles, c->num_cus);
-    (a.tail ? kernt : kern)<<<grid, 64 * lf::waves(LF_NL, LF_SW), lds, c->stream>>>(a);
-    ls.base += (unsigned long long)ls.ntiles + grid;
-    LSSP_HIP(hipGetLastError());
-    return LSSP_AMD_OK;
-}
-
-// one sweep of li (which: 0 L, 1 U) from its rhs stream; OUT 2: out = the U
-// rhs stream, OUT 1: natural order (tail: the product after the tiles)
-int linef_sweep(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
-                const LineTail *tail = nullptr)
-{
-    const LineSweep &ls = which ? li.U : li.L;
-    FillArgs a{};
-    a.nx = ls.nx;
-    a.ny = ls.ny;
-    a.ntiles = ls.ntiles;
-    a.n = (long)ls.nx * ls.ny * ls.nz;
-    a.tiles = ls.d_tiles;
-    a.coef = ls.d_coef;
-    a.rhs = stream;
-    a.out = out;
-    a.hk = li.d_hk;
-    a.hj = li.d_hj;
-    a.hk_stride = li.hk_stride;
-    a.hj_stride = li.hj_stride;
-    a.claim = ls.d_claim;
-    a.base = ls.base;
-    a.order = ls.d_order;
-    a.mirror = which;
-    a.err = c->d_err;
-    a.guard = c->guard;
-    a.tail = tail != nullptr && outk == 1;
-    if (a.tail) a.tl = *tail;
-    if (outk == 2) return ls.NA == 6 ? linef_launch_t<6, 2>(c, ls, a) : linef_launch_t<7, 2>(c, ls, a);
-    return ls.NA == 6 ? linef_launch_t<6, 1>(c, ls, a) : linef_launch_t<7, 1>(c, ls, a);
+    static LineKernels ks{k_linef<NA, OUT, LF_NL, LINEF_D, LINEF_DH, LF_SW>,
+                          k_linef<NA, OUT, LF_NL, LINEF_D, LINEF_DH, LF_SW, OUT == 1>, lds0, ldst,
+                          64 * lf::waves(LF_NL, LF_SW)};
+    return line_launch(c, ls, a, ks);
 }
 }  // namespace
 
-int launch_linefill_apply(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs)
+int launch_linef(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
+                 const LineTail *tail)
 {
-    if (li.g2) return launch_lineg(c, li, 0, x, rhs);
-    LSSP_TRY(linef_gather(c, li.L, 0, rhs, li.d_lstream));
-    LSSP_TRY(linef_sweep(c, li, 0, li.d_lstream, li.d_ustream, 2));
-    return linef_sweep(c, li, 1, li.d_ustream, x, 1);
-}
-
-// the apply with the U sweep's tail product (launch_line_apply_spmv prepared T);
-// returns the tail waves of the launch (each ends on one failed chunk claim)
-int launch_linefill_apply_tail(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs, const LineTail &T,
-                               long *tail_waves)
-{
-    LSSP_TRY(linef_gather(c, li.L, 0, rhs, li.d_lstream));
-    LSSP_TRY(linef_sweep(c, li, 0, li.d_lstream, li.d_ustream, 2));
-    LSSP_TRY(linef_sweep(c, li, 1, li.d_ustream, x, 1, &T));
-    *tail_waves = (long)std::min(li.U.ntiles, c->num_cus);  // (the tail's claimants: workgroups)
-    return LSSP_AMD_OK;
+    const LineSweep &ls = which ? li.U : li.L;
+    const LineArgs a = line_args(c, li, which, stream, out, outk, tail);
+    if (outk == 2) return ls.NA == 6 ? linef_launch_t<6, 2>(c, ls, a) : linef_launch_t<7, 2>(c, ls, a);
+    return ls.NA == 6 ? linef_launch_t<6, 1>(c, ls, a) : linef_launch_t<7, 1>(c, ls, a);
 }
 
 // lssp_amd_iluk_refactor: FillCoef::build + fill_upload on the device.  Workgroup
@@ -1311,14 +1183,6 @@ int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, 
     }
     li.lstream_of = nullptr;
     return LSSP_AMD_OK;
-}
-
-int launch_linefill_sweep(lssp_amd_ctx *c, const LineILU &li, int which, double *x, const double *rhs)
-{
-    if (li.g2) return launch_lineg(c, li, which ? 2 : 1, x, rhs);
-    double *st = which ? li.d_ustream : li.d_lstream;
-    LSSP_TRY(linef_gather(c, which ? li.U : li.L, which, rhs, st));
-    return linef_sweep(c, li, which, st, x, 1);
 }
 
 }  // namespace lssp_amd

@@ -129,7 +129,7 @@ static bool detect_grid(int n, const std::vector<int> &Lp, const std::vector<int
 // k_line2's plane skew: compute wave w owns planes 4w .. 4w+3 and runs
 // (LV-1) w levels later, so the k-input of a wave's first plane is one whole
 // step (LV levels) old
-static inline int line_sigma(int LV, int P, int p) { return LV >= 2 ? (LV - 1) * (p / 4) : 0; }
+static inline int line_sigma(int LV, int p) { return (LV - 1) * (p / 4); }
 
 // rows of a tile (nj lines, np planes) valid at level s, plane p: lanes [lo, hi]
 // (row i = s - l - p - sigma(p))
@@ -196,7 +196,7 @@ static int build_tiles(const LineGeom &g, int P, int NJ, int LV, int W, std::vec
             t.np = kt[K].second;
             const bool kin = t.k0 > 0 && g.kin[t.k0];
             t.flags = (kin ? LT_KIN : 0) | (J > 0 ? LT_JIN : 0) | (J < W - 1 ? LT_JOUT : 0);
-            t.T = g.nx + t.nj + t.np - 2 + line_sigma(LV, P, t.np - 1);
+            t.T = g.nx + t.nj + t.np - 2 + line_sigma(LV, t.np - 1);
             t.T = (t.T + LV - 1) / LV * LV;
             t.tk = kin ? (K - 1) * W + J : -1;
             t.tj = J > 0 ? K * W + J - 1 : -1;
@@ -213,21 +213,21 @@ static int build_tiles(const LineGeom &g, int P, int NJ, int LV, int W, std::vec
 // row's NA coefficients {c_k, c_j, c_i(, diag)} together.  Fixed strides keep
 // every role's addressing to a per-lane base plus immediate offsets.
 // + slack for the loaders' whole 1 KB pieces past the last block
-static inline size_t coef_len(const LineSweep &ls) { return (size_t)ls.rows_total * ls.NA + 16 * 1024 / 8; }
+constexpr long STREAM_SLACK = 16 * 1024 / 8;
+size_t line_coef_len(const LineSweep &ls) { return (size_t)ls.rows_total * ls.NA + STREAM_SLACK; }
 
-// The part that depends on the grid alone: every tile's place in the streams,
-// the tile table, the claim counter and order, and the coefficient stream's
-// allocation (its values: upload_sweep from host factors, or k_coef_refill).
-static int layout_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<LineTile> &tiles, int NA, LineSweep &ls)
+// The part of a sweep (either kind) that depends on the grid alone (internal.h);
+// the coefficient stream's values: upload_sweep / fill_upload from host
+// factors, or zeroed for k_coef_refill / k_linef_refill.
+int line_layout(lssp_amd_ctx *, const LineGeom &g, const std::vector<LineTile> &tiles, int NA, int W, int wj, int wk,
+                LineSweep &ls)
 {
-    const int P = ls.P, LV = ls.LV;
     std::vector<LineTile> tt = tiles;
     long rows_total = 0;
     int tmax = 0;
     for (LineTile &t : tt) {
-        t.roff = 0;
         t.cbase = rows_total;
-        rows_total += (long)t.T * P * t.nj;
+        rows_total += (long)t.T * ls.P * t.nj;
         tmax = std::max(tmax, t.T);
     }
     ls.nx = g.nx;
@@ -239,27 +239,60 @@ static int layout_sweep(lssp_amd_ctx *c, const LineGeom &g, const std::vector<Li
     ls.NA = NA;
     LSSP_HIP(hipMalloc(&ls.d_tiles, sizeof(LineTile) * tt.size()));
     LSSP_HIP(hipMemcpy(ls.d_tiles, tt.data(), sizeof(LineTile) * tt.size(), hipMemcpyHostToDevice));
-    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * coef_len(ls)));
+    LSSP_HIP(hipMalloc(&ls.d_coef, sizeof(double) * line_coef_len(ls)));
     LSSP_HIP(hipMalloc(&ls.d_claim, sizeof(unsigned long long)));
     LSSP_HIP(hipMemset(ls.d_claim, 0, sizeof(unsigned long long)));
-    if (LV >= 2) {
-        // k_line2 claims tiles by anti-diagonal J + K (then K): a claimed tile's
-        // producers (J-1, K) and (J, K-1) were claimed before it, and the
-        // workgroups hold tiles of the advancing wavefront instead of tiles
-        // many hops ahead of it (row order: the first 256 claims of a 216^3 sweep
-        // reach K = 18, whose tiles wait ~30 hops before they can start).
-        const int W = (g.ny + ls.NJ - 1) / ls.NJ, nt = (int)tt.size();
-        std::vector<int> ord(nt);
-        for (int q = 0; q < nt; q++) ord[q] = q;
-        std::stable_sort(ord.begin(), ord.end(), [W](int x, int y) {
-            const int dx = x % W + x / W, dy = y % W + y / W;
-            return dx != dy ? dx < dy : x < y;
-        });
-        LSSP_HIP(hipMalloc(&ls.d_order, sizeof(int) * nt));
-        LSSP_HIP(hipMemcpy(ls.d_order, ord.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
-    }
+    // Tiles are claimed in the order of their earliest start, wj J + wk K (then
+    // K): a claimed tile's producers (J-1, K) and (J, K-1) were claimed before
+    // it, and the workgroups hold tiles of the advancing wavefront instead of
+    // tiles many hops ahead of it (row order: the first 256 claims of a 216^3
+    // ILU(0) sweep reach K = 18, whose tiles wait ~30 hops before they can start).
+    const int nt = (int)tt.size();
+    std::vector<int> ord(nt);
+    for (int q = 0; q < nt; q++) ord[q] = q;
+    std::stable_sort(ord.begin(), ord.end(), [=](int x, int y) {
+        const long kx = (long)(x % W) * wj + (long)(x / W) * wk, ky = (long)(y % W) * wj + (long)(y / W) * wk;
+        return kx != ky ? kx < ky : x < y;
+    });
+    LSSP_HIP(hipMalloc(&ls.d_order, sizeof(int) * nt));
+    LSSP_HIP(hipMemcpy(ls.d_order, ord.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
     ls.h_tiles = std::move(tt);
-    (void)c;
+    return LSSP_AMD_OK;
+}
+
+// After both layouts (internal.h): the L sweep writes its output into the U
+// sweep's rhs stream, so each L tile gets the base row of its mirror U tile
+// (U tile (W-1-J, S-1-K) <-> L tile (J, K)); the U rhs stream and the L rhs
+// stream of the apply (the gathers fill the valid rows, the others stay +0.0),
+// with the loaders' slack; the hand-off buffers, shared by both sweeps (they
+// never run at once) and armed with the sentinel.
+int finish_line_tiles(lssp_amd_ctx *c, LineILU &li, long hk_stride, long hj_stride)
+{
+    const int W = li.W, S = li.S;
+    for (int K = 0; K < S; K++)
+        for (int J = 0; J < W; J++) {
+            LineTile &l = li.L.h_tiles[(size_t)K * W + J];
+            l.ut = (S - 1 - K) * W + (W - 1 - J);
+            l.ubase = li.U.h_tiles[l.ut].cbase;
+        }
+    LSSP_HIP(hipMemcpy(li.L.d_tiles, li.L.h_tiles.data(), sizeof(LineTile) * li.L.h_tiles.size(),
+                       hipMemcpyHostToDevice));
+    for (int which = 0; which < 2; which++) {
+        double *&st = which ? li.d_ustream : li.d_lstream;
+        const size_t len = sizeof(double) * ((which ? li.U : li.L).rows_total + STREAM_SLACK);
+        LSSP_HIP(hipMalloc(&st, len));
+        LSSP_HIP(hipMemset(st, 0, len));
+    }
+    li.tmax = std::max(li.L.tmax, li.U.tmax);
+    li.hk_stride = hk_stride;
+    li.hj_stride = hj_stride;
+    li.ntiles = li.L.ntiles;
+    li.hk_n = li.hk_stride * li.ntiles;
+    li.hj_n = li.hj_stride * li.ntiles;
+    LSSP_HIP(hipMalloc(&li.d_hk, sizeof(double) * li.hk_n));
+    LSSP_HIP(hipMalloc(&li.d_hj, sizeof(double) * li.hj_n));
+    LSSP_TRY(line_rearm(c, li));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
     return LSSP_AMD_OK;
 }
 
@@ -268,7 +301,7 @@ static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc &src, 
 {
     const int nx = g.nx, P = ls.P, LV = ls.LV, NA = ls.NA;
     const std::vector<LineTile> &tt = ls.h_tiles;
-    std::vector<double> coef(coef_len(ls), 0.0);
+    std::vector<double> coef(line_coef_len(ls), 0.0);
     parallel_for((long)tt.size(), [&](long t0, long t1) {
     for (long ti = t0; ti < t1; ti++) {
         const LineTile &t = tt[ti];
@@ -276,7 +309,7 @@ static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc &src, 
             double *blk = coef.data() + (size_t)(t.cbase + (long)s * P * t.nj) * NA;
             for (int p = 0; p < t.np; p++) {
                 int lo, hi;
-                const int sg = line_sigma(LV, P, p);
+                const int sg = line_sigma(LV, p);
                 step_range(nx, t.nj, t.np, s, p, sg, lo, hi);
                 for (int l = lo; l <= hi; l++) {
                     const long i = s - l - p - sg;
@@ -359,45 +392,21 @@ static int build_line_tiles(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc *c
     li.LV = li.L.LV = li.U.LV = LV;
     li.W = W;
     li.S = S;
-    LSSP_TRY(layout_sweep(c, g, Lt, NAL, li.L));
+    // claims by anti-diagonal J + K
+    LSSP_TRY(line_layout(c, g, Lt, NAL, W, 1, 1, li.L));
     LineGeom gu = g;
     for (int k = 0; k < g.nz; k++) gu.kin[k] = k > 0 ? g.kin[g.nz - k] : 0;
-    LSSP_TRY(layout_sweep(c, gu, Ut, NAD, li.U));
+    LSSP_TRY(line_layout(c, gu, Ut, NAD, W, 1, 1, li.U));
     if (cl && cu) {
         LSSP_TRY(upload_sweep(c, g, *cl, li.L));
         LSSP_TRY(upload_sweep(c, gu, *cu, li.U));
     } else {
-        LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * coef_len(li.L), c->stream));
-        LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * coef_len(li.U), c->stream));
+        LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * line_coef_len(li.L), c->stream));
+        LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * line_coef_len(li.U), c->stream));
     }
-    // the L sweep writes its output into the U sweep's rhs stream: per L tile
-    // the base row of its mirror U tile
-    for (int K = 0; K < S; K++)
-        for (int J = 0; J < W; J++) {
-            LineTile &l = li.L.h_tiles[(size_t)K * W + J];
-            l.ut = (S - 1 - K) * W + (W - 1 - J);
-            l.ubase = li.U.h_tiles[l.ut].cbase;
-        }
-    LSSP_HIP(hipMemcpy(li.L.d_tiles, li.L.h_tiles.data(), sizeof(LineTile) * li.L.h_tiles.size(),
-                       hipMemcpyHostToDevice));
-    // U rhs stream (written by the L sweep) and the hand-off buffers, shared by
-    // both sweeps (they never run at once) and armed with the sentinel
-    LSSP_HIP(hipMalloc(&li.d_ustream, sizeof(double) * (li.U.rows_total + 16 * 1024 / 8)));
-    LSSP_HIP(hipMemset(li.d_ustream, 0, sizeof(double) * (li.U.rows_total + 16 * 1024 / 8)));  // invalid rows stay +0.0
-    // the apply's L sweep reads its rhs as a stream too (k_line_rhs fills the valid rows)
-    LSSP_HIP(hipMalloc(&li.d_lstream, sizeof(double) * (li.L.rows_total + 16 * 1024 / 8)));
-    LSSP_HIP(hipMemset(li.d_lstream, 0, sizeof(double) * (li.L.rows_total + 16 * 1024 / 8)));
-    li.tmax = std::max(li.L.tmax, li.U.tmax);
-    li.hk_stride = (long)li.tmax * NJ;
-    li.hj_stride = (long)li.tmax * P;
-    li.ntiles = (int)Lt.size();
-    li.hk_n = li.hk_stride * li.ntiles;
-    li.hj_n = li.hj_stride * li.ntiles;
-    LSSP_HIP(hipMalloc(&li.d_hk, sizeof(double) * li.hk_n));
-    LSSP_HIP(hipMalloc(&li.d_hj, sizeof(double) * li.hj_n));
-    LSSP_TRY(line_rearm(c, li));
-    LSSP_HIP(hipStreamSynchronize(c->stream));
-    return LSSP_AMD_OK;
+    // hand-off rows: one per level, NJ k entries and P j entries each
+    const long tmax = std::max(li.L.tmax, li.U.tmax);
+    return finish_line_tiles(c, li, tmax * NJ, tmax * P);
 }
 
 int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
@@ -585,35 +594,8 @@ void free_line_sweep(LineILU &li)
 }
 
 // ---------------------------------------------------------------------------
-// device
-// ---------------------------------------------------------------------------
-struct LineArgs {
-    int nx, ny, ntiles;
-    long n;
-    const LineTile *tiles;
-    const double *coef;
-    const double *rhs;      // natural order (RHS_NAT) or the U rhs stream
-    double *out;            // OUT 1: natural-order output; OUT 2: the U rhs stream
-    double *hk, *hj;
-    long hk_stride, hj_stride;
-    unsigned long long *claim;
-    unsigned long long base;
-    const int *order;       // k_line2: tile of each claim (wavefront order), nullptr: claim order
-    int mirror;             // U sweep: natural row = n-1 - sweep row
-    int *err;
-    // diagnostics (LSSP_AMD_LINE_TRACE): per tile {claim, step 0, end, re-polls,
-    // xcc}; per step of tile ttile {compute start, compute end, poller busy,
-    // loader wait, loader issue, storer busy}
-    unsigned long long *trace;
-    int ttile;
-    int diag;  // LSSP_AMD_LINE_DIAG timing experiments (wrong results when != 0)
-    const double *guard;  // lssp_amd_ctx::guard
-    int tail;     // k_line2 OUT 1: run the product tl after the tiles (write-through output, tile counts)
-    LineTail tl;
-};
-
-// ---------------------------------------------------------------------------
-// k_line2: two levels per workgroup step (the default line sweep)
+// device: k_line2, two levels per workgroup step (arguments: LineArgs,
+// linesweep_dev.h)
 // ---------------------------------------------------------------------------
 // A tile is nj <= 16 lines x np <= 8 planes, 128 rows per level.  Two compute
 // waves: wave w owns planes 4w .. 4w+3; lane (g, l) = 16 g + l owns line l of
@@ -690,9 +672,9 @@ __global__ __launch_bounds__(64 * l2::waves(P, NL, SW)) void k_line2(LineArgs a)
     constexpr int LA = 2;  // the loaders complete step s+LA's slot during step s
     constexpr int R = D + 1;
     constexpr int RSL = rsl<OUT, LV>();
-    constexpr int NITEM = SL::NPC + SL::NRP;  // DMA instructions per step, shared by the loaders
-    constexpr int KPER = (NITEM + NL - 1) / NL;
     constexpr int S0 = -2 * ((D + 2) / 2);  // first step of every role (even, <= -D-1)
+    constexpr int NITEM = SL::NPC + SL::NRP;
+    constexpr int KPER = (NITEM + NL - 1) / NL;
     static_assert(DH >= 2 && DH < D && (D - LA) * KPER <= 63 && 2 * (DH - 1) <= 63, "leads");
     static_assert(OUT == 1 || OUT == 2, "out");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -727,7 +709,7 @@ __global__ __launch_bounds__(64 * l2::waves(P, NL, SW)) void k_line2(LineArgs a)
             // claims in wavefront order (LineSweep::d_order): every tile's producers
             // have a smaller anti-diagonal J + K and were claimed before it
             const int c = (int)(atomicAdd(a.claim, 1ull) - a.base);
-            *s_tile = c < a.ntiles ? (a.order ? a.order[c] : c) : a.ntiles;
+            *s_tile = c < a.ntiles ? a.order[c] : a.ntiles;
         }
         __syncthreads();
         const int t = __builtin_amdgcn_readfirstlane(*s_tile);
@@ -1035,7 +1017,7 @@ __global__ __launch_bounds__(64 * l2::waves(P, NL, SW)) void k_line2(LineArgs a)
                         const int q = 8 * B + m;
                         const int i = q - l - p - sig(p);
                         const double x = res[(q & (RSL - 1)) * ROWS + p * NJ + l];
-                        if (!(a.diag & 1) && p < np && l < nj && (unsigned)i < (unsigned)nx) {
+                        if (p < np && l < nj && (unsigned)i < (unsigned)nx) {
                             double *o = a.out + (a.mirror ? nb(p, l) - i : nb(p, l) + i);
                             if (tail) st_sc1d(o, x);  // read by the tail product on other CUs
                             else *o = x;
@@ -1060,14 +1042,14 @@ __global__ __launch_bounds__(64 * l2::waves(P, NL, SW)) void k_line2(LineArgs a)
                 constexpr int PS = LV * ROWS / 64 / SW;
                 static_assert(LV * ROWS % (64 * SW) == 0, "chunks");
                 double *po[PS];
-                int vlo[PS], lvs[PS], roff[PS];
+                int vlo[PS], lvs[PS], rix[PS];
 #pragma unroll
                 for (int u = 0; u < PS; u++) {
                     const int k = (w + u * SW) * 64 + lane;
                     const int lv = k / ROWS, p = (k >> 4) & (P - 1), l = k & (NJ - 1);
                     const int pp = min(p, np - 1), lq = min(l, nj - 1);
                     lvs[u] = lv;
-                    roff[u] = (lv * P + p) * NJ + l;
+                    rix[u] = (lv * P + p) * NJ + l;
                     vlo[u] = p < np && l < nj ? l + p + sig(p) : 1 << 30;  // valid iff 0 <= v - vlo < nx
                     const long Cp = (long)nx + nj + np - 3 + sig(pp) + sig(np - 1 - pp);
                     po[u] = a.out + d.ubase + Cp * SB + (long)(np - 1 - pp) * nj + (nj - 1 - lq);
@@ -1079,8 +1061,8 @@ __global__ __launch_bounds__(64 * l2::waves(P, NL, SW)) void k_line2(LineArgs a)
 #pragma unroll
                         for (int u = 0; u < PS; u++) {
                             const int v = LV * q + lvs[u];
-                            const double x = res[(v & (RSL - 1)) * ROWS + (roff[u] & (ROWS - 1))];
-                            if (!(a.diag & 33) && (unsigned)(v - vlo[u]) < (unsigned)nx) po[u][-SB * v] = x;
+                            const double x = res[(v & (RSL - 1)) * ROWS + (rix[u] & (ROWS - 1))];
+                            if ((unsigned)(v - vlo[u]) < (unsigned)nx) po[u][-SB * v] = x;
                         }
                         rearm(q);
                     }
@@ -1092,7 +1074,7 @@ __global__ __launch_bounds__(64 * l2::waves(P, NL, SW)) void k_line2(LineArgs a)
     }
     if constexpr (TL) {
         if (a.tail) {  // no tile left for this workgroup: its waves run the tail product
-            int *soff = reinterpret_cast<int *>(smem);  // (the ring's LDS is free now; launch_line2_t reserves TAIL_LDS_BYTES)
+            int *soff = reinterpret_cast<int *>(smem);  // (the ring's LDS is free now; line_tail_lds reserves it)
             __syncthreads();  // (the loop's last barrier already passed; the ring is free)
             if (threadIdx.x < a.tl.ndiag) soff[threadIdx.x] = a.tl.off[threadIdx.x];
             __syncthreads();
@@ -1292,65 +1274,10 @@ constexpr int line2_d() { return LV == 4 ? 4 : OUT == 1 ? LINE2_D_U : LINE2_D; }
 #endif
 template <int LV, int OUT>
 constexpr int line2_dh() { return LV == 4 ? 2 : OUT == 1 ? LINE2_DH_U : LINE2_DH; }
-template <int P, int LV, int NA, int OUT, bool TRACE, bool TL = false>
-static int launch_line2_k(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &g, int lds)
-{
-    auto kern = k_line2<P, LV, NA, OUT, LINE2_NL, line2_d<LV, OUT>(), line2_dh<LV, OUT>(), LINE2_SW, TRACE, TL>;
-    static int attr = 0;
-    if (lds > attr) {
-        LSSP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr = lds;
-    }
-    const int grid = std::min(ls.ntiles, c->num_cus);
-    kern<<<grid, 64 * l2::waves(P, LINE2_NL, LINE2_SW), lds, c->stream>>>(g);
-    ls.base += (unsigned long long)ls.ntiles + grid;
-    LSSP_HIP(hipGetLastError());
-    return LSSP_AMD_OK;
-}
 
-template <int P, int LV, int NA, int OUT>
-static int launch_line2_t(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &a)
-{
-    // (a sweep with natural-order output and the tail product reserves what the product needs)
-    constexpr int lds0 = l2::lds_bytes<NA, OUT, line2_d<LV, OUT>(), P, LV>();
-    constexpr int ldst = OUT == 1 && lds0 < TAIL_LDS_BYTES(0) ? TAIL_LDS_BYTES(0) : lds0;
-    static_assert(ldst <= 160 * 1024, "LDS");
-    const int lds = a.tail ? ldst : lds0;
-    static_assert(OUT != 1 || l2::waves(P, LINE2_NL, LINE2_SW) >= TAIL_WAVES, "the tail product's roles");
-    // diagnostics only: LSSP_AMD_LINE_TRACE=path[:tile] appends one JSON line per sweep
-    static const char *trp = getenv("LSSP_AMD_LINE_TRACE");
-    if constexpr (OUT == 1)
-        if (a.tail) return launch_line2_k<P, LV, NA, OUT, false, true>(c, ls, a, lds);  // (no trace variant)
-    if (!trp) return launch_line2_k<P, LV, NA, OUT, false>(c, ls, a, lds);
-    LineArgs g = a;
-    const size_t tn = 8 * (size_t)ls.ntiles + 8 * (size_t)ls.tmax + 64;
-    const char *colon = strrchr(trp, ':');
-    g.ttile = colon ? atoi(colon + 1) : ls.ntiles / 2;
-    LSSP_HIP(hipMalloc(&g.trace, sizeof(unsigned long long) * tn));
-    LSSP_HIP(hipMemsetAsync(g.trace, 0, sizeof(unsigned long long) * tn, c->stream));
-    const int grid = std::min(ls.ntiles, c->num_cus);
-    LSSP_TRY((launch_line2_k<P, LV, NA, OUT, true>(c, ls, g, lds)));
-    std::vector<unsigned long long> h(tn);
-    LSSP_HIP(hipMemcpyAsync(h.data(), g.trace, sizeof(unsigned long long) * tn, hipMemcpyDeviceToHost, c->stream));
-    LSSP_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(g.trace);
-    std::string path(trp, colon ? colon - trp : strlen(trp));
-    FILE *f = fopen(path.c_str(), "a");
-    if (f) {
-        fprintf(f, "{\"mirror\": %d, \"ntiles\": %d, \"W\": %d, \"ttile\": %d, \"T\": %d, \"LV\": %d, \"grid\": %d, "
-                   "\"data\": [",
-                a.mirror, ls.ntiles, (ls.ny + ls.NJ - 1) / ls.NJ, g.ttile, ls.h_tiles[g.ttile].T / LV, LV, grid);
-        for (size_t i = 0; i < tn; i++) fprintf(f, "%s%llu", i ? ", " : "", h[i]);
-        fprintf(f, "]}\n");
-        fclose(f);
-    }
-    return LSSP_AMD_OK;
-}
-
-// k_line2 sweep of ls: rhs from a stream; OUT 2: out = the U rhs stream, OUT 1: natural order
-// (tail: the product run by the sweep's workgroups after its tiles, OUT 1 only)
-static int launch_line2(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
-                        const LineTail *tail = nullptr)
+// the arguments and the launch of a tiled sweep of either kind (internal.h)
+LineArgs line_args(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
+                   const LineTail *tail)
 {
     const LineSweep &ls = which ? li.U : li.L;
     LineArgs a{};
@@ -1372,27 +1299,106 @@ static int launch_line2(lssp_amd_ctx *c, const LineILU &li, int which, const dou
     a.mirror = which;
     a.err = c->d_err;
     a.guard = c->guard;
-    {
-        const char *dg = getenv("LSSP_AMD_LINE_DIAG");
-        a.diag = dg ? atoi(dg) : 0;
-    }
     a.tail = tail != nullptr && outk == 1;
     if (a.tail) a.tl = *tail;
+    return a;
+}
+
+int line_launch(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &a, LineKernels &k)
+{
+    const int t = a.tail ? 1 : 0, lds = t ? k.ldst : k.lds0;
+    void (*const kern)(LineArgs) = t ? k.kernt : k.kern;
+    if (!k.sized[t].load(std::memory_order_acquire)) {  // (set twice by two racing threads: harmless)
+        LSSP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        k.sized[t].store(true, std::memory_order_release);
+    }
+    const int grid = std::min(ls.ntiles, c->num_cus);
+    kern<<<grid, k.block, lds, c->stream>>>(a);
+    ls.base += (unsigned long long)ls.ntiles + grid;
+    LSSP_HIP(hipGetLastError());
+    return LSSP_AMD_OK;
+}
+
+template <int P, int LV, int NA, int OUT>
+static int launch_line2_t(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &a)
+{
+    constexpr int D = line2_d<LV, OUT>(), DH = line2_dh<LV, OUT>(), block = 64 * l2::waves(P, LINE2_NL, LINE2_SW);
+    constexpr int lds0 = l2::lds_bytes<NA, OUT, D, P, LV>(), ldst = OUT == 1 ? line_tail_lds(lds0) : lds0;
+    static_assert(ldst <= 160 * 1024, "LDS");
+    static_assert(OUT != 1 || l2::waves(P, LINE2_NL, LINE2_SW) >= TAIL_WAVES, "the tail product's roles");
+    // diagnostics only: LSSP_AMD_LINE_TRACE=path[:tile] appends one JSON line per sweep
+    static const char *trp = getenv("LSSP_AMD_LINE_TRACE");
+    static LineKernels ks{k_line2<P, LV, NA, OUT, LINE2_NL, D, DH, LINE2_SW, false>,
+                          k_line2<P, LV, NA, OUT, LINE2_NL, D, DH, LINE2_SW, false, OUT == 1>, lds0, ldst, block};
+    if (!trp || a.tail) return line_launch(c, ls, a, ks);  // (no trace variant with the tail product)
+    static LineKernels kt{k_line2<P, LV, NA, OUT, LINE2_NL, D, DH, LINE2_SW, true>,
+                          k_line2<P, LV, NA, OUT, LINE2_NL, D, DH, LINE2_SW, true>, lds0, lds0, block};
+    LineArgs g = a;
+    const size_t tn = 8 * (size_t)ls.ntiles + 8 * (size_t)ls.tmax + 64;
+    const char *colon = strrchr(trp, ':');
+    g.ttile = colon ? atoi(colon + 1) : ls.ntiles / 2;
+    LSSP_HIP(hipMalloc(&g.trace, sizeof(unsigned long long) * tn));
+    LSSP_HIP(hipMemsetAsync(g.trace, 0, sizeof(unsigned long long) * tn, c->stream));
+    const int grid = std::min(ls.ntiles, c->num_cus);
+    LSSP_TRY(line_launch(c, ls, g, kt));
+    std::vector<unsigned long long> h(tn);
+    LSSP_HIP(hipMemcpyAsync(h.data(), g.trace, sizeof(unsigned long long) * tn, hipMemcpyDeviceToHost, c->stream));
+    LSSP_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(g.trace);
+    std::string path(trp, colon ? colon - trp : strlen(trp));
+    FILE *f = fopen(path.c_str(), "a");
+    if (f) {
+        fprintf(f, "{\"mirror\": %d, \"ntiles\": %d, \"W\": %d, \"ttile\": %d, \"T\": %d, \"LV\": %d, \"grid\": %d, "
+                   "\"data\": [",
+                a.mirror, ls.ntiles, (ls.ny + ls.NJ - 1) / ls.NJ, g.ttile, ls.h_tiles[g.ttile].T / LV, LV, grid);
+        for (size_t i = 0; i < tn; i++) fprintf(f, "%s%llu", i ? ", " : "", h[i]);
+        fprintf(f, "]}\n");
+        fclose(f);
+    }
+    return LSSP_AMD_OK;
+}
+
+// k_line2 sweep of li's factor `which` from its rhs stream (arguments: line_args)
+static int launch_line2(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
+                        const LineTail *tail = nullptr)
+{
+    const LineSweep &ls = which ? li.U : li.L;
+    const LineArgs a = line_args(c, li, which, stream, out, outk, tail);
     // (the kernel is generic in LV; four levels per step measured slower)
     if (outk == 2) return ls.NA == 3 ? launch_line2_t<8, 2, 3, 2>(c, ls, a) : launch_line2_t<8, 2, 4, 2>(c, ls, a);
     return ls.NA == 3 ? launch_line2_t<8, 2, 3, 1>(c, ls, a) : launch_line2_t<8, 2, 4, 1>(c, ls, a);
 }
 
+// ---- apply and single sweeps of either tiled kind ---------------------------
+static int line_gather(lssp_amd_ctx *c, const LineILU &li, int which, const double *rhs, double *stream)
+{
+    const LineSweep &ls = which ? li.U : li.L;
+    return li.kind == 1 ? launch_linef_gather(c, ls, which, rhs, stream) : launch_line_gather(c, ls, which, rhs, stream);
+}
+static int line_sweep_of(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
+                         const LineTail *tail = nullptr)
+{
+    return li.kind == 1 ? launch_linef(c, li, which, stream, out, outk, tail)
+                        : launch_line2(c, li, which, stream, out, outk, tail);
+}
+// gather (unless the L stream holds rhs already: launch_line_gather_ew, kind 0
+// only), L sweep -> the U rhs stream, U sweep -> x (tail: then the product)
+static int line_apply_seq(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs, const LineTail *tail)
+{
+    const bool ready = li.kind == 0 && rhs == li.lstream_of;
+    li.lstream_of = nullptr;
+    if (!ready) LSSP_TRY(line_gather(c, li, 0, rhs, li.d_lstream));
+    LSSP_TRY(line_sweep_of(c, li, 0, li.d_lstream, li.d_ustream, 2));
+    return line_sweep_of(c, li, 1, li.d_ustream, x, 1, tail);
+}
+
 int launch_line_apply(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs)
 {
-    const bool ready = rhs == li.lstream_of;  // the stream holds rhs already (launch_line_gather_ew)
-    li.lstream_of = nullptr;
-    if (li.g2) return launch_lineg(c, li, 0, x, rhs);
-    if (li.kind == 1) return launch_linefill_apply(c, li, x, rhs);
-    // k_line2: gather, L sweep -> the U rhs stream, U sweep -> x
-    if (!ready) LSSP_TRY(launch_line_gather(c, li.L, 0, rhs, li.d_lstream));
-    LSSP_TRY(launch_line2(c, li, 0, li.d_lstream, li.d_ustream, 2));
-    return launch_line2(c, li, 1, li.d_ustream, x, 1);
+    if (li.g2) {
+        li.lstream_of = nullptr;
+        return launch_lineg(c, li, 0, x, rhs);
+    }
+    return line_apply_seq(c, li, x, rhs, nullptr);
 }
 
 unsigned *tail_dbg_host = nullptr;  // LSSP_AMD_TAIL_DIAG (lssp_amd_debug_words)
@@ -1485,19 +1491,10 @@ int launch_line_apply_spmv(lssp_amd_ctx *c, const LineILU &li, double *x, const 
         tail_dbg_host = dbg_h;
         T.dbg = dbg_d;
     }
-    long tail_waves = (long)std::min(li.U.ntiles, c->num_cus);  // (the tail's claimants: workgroups)
-    const bool ready = rhs == li.lstream_of;
-    li.lstream_of = nullptr;
-    if (li.kind == 1) {  // the 7-/5-point ILU(1) line sweeps (linefill.hip)
-        LSSP_TRY(launch_linefill_apply_tail(c, li, x, rhs, T, &tail_waves));
-    } else {
-        if (!ready) LSSP_TRY(launch_line_gather(c, li.L, 0, rhs, li.d_lstream));
-        LSSP_TRY(launch_line2(c, li, 0, li.d_lstream, li.d_ustream, 2));
-        LSSP_TRY(launch_line2(c, li, 1, li.d_ustream, x, 1, &T));
-    }
-    // chunks are claimed in pairs and every workgroup of the grid ends on one
-    // failed pair claim; every U tile counted once
-    li.tbase += tail_claims(nblk, tail_waves);
+    LSSP_TRY(line_apply_seq(c, li, x, rhs, &T));
+    // chunks are claimed in groups and every workgroup of the U sweep's grid (the
+    // tail's claimants) ends on one failed claim; every U tile counted once
+    li.tbase += tail_claims(nblk, (long)std::min(li.U.ntiles, c->num_cus));
     li.kepoch++;
     return LSSP_AMD_OK;
 }
@@ -1506,11 +1503,10 @@ int launch_line_sweep(lssp_amd_ctx *c, const LineILU &li, int which, double *x, 
 {
     li.lstream_of = nullptr;
     if (li.g2) return launch_lineg(c, li, which ? 2 : 1, x, rhs);
-    if (li.kind == 1) return launch_linefill_sweep(c, li, which, x, rhs);
     // one sweep: its rhs gathered into its own stream, natural-order output
     double *st = which ? li.d_ustream : li.d_lstream;
-    LSSP_TRY(launch_line_gather(c, which ? li.U : li.L, which, rhs, st));
-    return launch_line2(c, li, which, st, x, 1);
+    LSSP_TRY(line_gather(c, li, which, rhs, st));
+    return line_sweep_of(c, li, which, st, x, 1);
 }
 
 }  // namespace lssp_amd

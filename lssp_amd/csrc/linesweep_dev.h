@@ -1,7 +1,9 @@
-// linesweep_dev.h -- device helpers shared by the line sweeps (linesweep.hip:
-// k_line2 for ILU(0); linefill.hip: k_linef for the 7-point ILU(1)
-// pattern): LDS-DMA issue, the workgroup barrier, agent-scope hand-off loads,
-// lane selects, DPP row shifts and the lane - 16 shuffle.
+// linesweep_dev.h -- what the two tiled line sweeps share on the device
+// (linesweep.hip: k_line2 for ILU(0); linefill.hip: k_linef for the 7-point
+// ILU(1) pattern).  Helpers: LDS-DMA issue, the workgroup barrier, agent-scope
+// hand-off loads, lane selects, DPP row shifts and the lane - 16 shuffle.  The
+// U sweep's tail product (LineTail, line_tail_wg).  And the kernel arguments
+// LineArgs of both sweeps (the end of this file).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -503,5 +505,38 @@ static __device__ void line_tail_wg(const LineTail &T, const double *x, int *err
     }
     if (dwr) *dwr = (unsigned)rticks;
 }
+
+// The arguments of the tiled sweeps k_line2 and k_linef (filled by line_args,
+// launched by line_launch: internal.h).  A workgroup claims tiles until none is
+// left; per tile its waves take their roles, one barrier per step of LV
+// levels: compute waves, NL loaders, 1 poller, SW storers.  The roles are per
+// kernel: shared as inlined templates they measured slower.
+struct LineArgs {
+    int nx, ny, ntiles;
+    long n;
+    const LineTile *tiles;
+    const double *coef;
+    const double *rhs;      // the sweep's rhs stream
+    double *out;            // OUT 1: natural-order output; OUT 2: the U rhs stream
+    double *hk, *hj;
+    long hk_stride, hj_stride;
+    unsigned long long *claim;
+    unsigned long long base;
+    const int *order;       // the tile of each claim (LineSweep::d_order)
+    int mirror;             // U sweep: natural row = n-1 - sweep row
+    int *err;
+    const double *guard;  // lssp_amd_ctx::guard
+    int tail;     // OUT 1: run the product tl after the tiles (write-through output, tile counts)
+    LineTail tl;
+    // (last, so that k_linef, which does not read them, keeps the argument
+    // offsets it was tuned with: in the middle they cost k_linef<7,1,TL> a VGPR)
+    // k_line2's diagnostics (LSSP_AMD_LINE_TRACE): per tile {claim, step 0, end,
+    // re-polls, xcc}; per step of tile ttile {compute start, compute end, poller
+    // busy, loader wait, loader issue, storer busy}
+    unsigned long long *trace;
+    int ttile;
+};
+// a sweep with the tail product reserves the LDS the product needs
+constexpr int line_tail_lds(int lds0) { return lds0 < TAIL_LDS_BYTES(0) ? TAIL_LDS_BYTES(0) : lds0; }
 
 }  // namespace lssp_amd

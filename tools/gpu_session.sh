@@ -18,7 +18,7 @@
 #   prof5            rocprofv3 --kernel-trace of config 5 (CG) + tools/kgaps.py
 #   config2 / config3 / config5 / general   tools/bench_configs.py bicgstab-iluk --grid 256 /
 #                    gmres-ilut / cg-thermal / general-ilu
-#   linediag=N[:LIB] tools/line_diag.py N 0 (optionally with LSSP_AMD_LIB=build/LIB.so)
+#   linediag=N[:LIB] tools/line_diag.py N (optionally with LSSP_AMD_LIB=build/LIB.so)
 #   linetrace=N      tools/line_trace.py N 150 -> line_trace_N.txt
 #   pk6trace=N       tools/pk6_trace.py N 60 ilut -> pk6_trace_N.txt
 #   serialdot        tools/serial_dot_probe.py -> serial_dot.txt
@@ -90,7 +90,7 @@ for step in "$@"; do
     ;;
   linediag=*)
     A=${step#linediag=}; N=${A%%:*}; LIB=; [ "$A" != "$N" ] && LIB=$PWD/build/${A#*:}.so
-    LSSP_AMD_LIB=$LIB timeout -k 10 200 python -u tools/line_diag.py "$N" 0 2>&1 | grep -v amdgpu.ids | tee -a $O/line_diag.txt || fail $step $?
+    LSSP_AMD_LIB=$LIB timeout -k 10 200 python -u tools/line_diag.py "$N" 2>&1 | grep -v amdgpu.ids | tee -a $O/line_diag.txt || fail $step $?
     ;;
   linetrace=*)
     N=${step#linetrace=}

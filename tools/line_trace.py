@@ -65,9 +65,6 @@ def summarise(rec):
 def main():
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 216
     tile = int(sys.argv[2]) if len(sys.argv) > 2 else 100
-    if len(sys.argv) > 3:  # LSSP_AMD_LINE_DIAG timing experiment (wrong results)
-        os.environ["LSSP_AMD_LINE_DIAG"] = sys.argv[3]
-        print(f"LSSP_AMD_LINE_DIAG={sys.argv[3]}")
     path = os.path.join(ROOT, "gpurun_out", "line_trace.jsonl")
     os.makedirs(os.path.dirname(path), exist_ok=True)
     if os.path.exists(path):
