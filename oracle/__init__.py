@@ -28,10 +28,11 @@ ORACLE_SO = os.path.join(HERE, "_build", "liboracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libref.so")
 
 # LSSP_SOLVER_TYPE / LSSP_PC_TYPE values (type-defs.h:63-101, :157-178)
-GMRES, LGMRES, RGMRES, BICGSTAB, CG = 0, 1, 2, 4, 7
+GMRES, LGMRES, RGMRES, RLGMRES, BICGSTAB, CG = 0, 1, 2, 3, 4, 7
 BICGSAFE, CGS, GPBICG, CR, CRS, BICRSTAB, BICRSAFE, GPBICR, QMRCGSTAB, TFQMR, ORTHOMIN = (
     6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17)
 BICGSTABL, IDRS = 5, 18  # l of BiCGSTAB(l) / s of IDR(s) are passed as `restart` (<= 0: 4)
+# k of LGMRES / RLGMRES is its own argument, `aug_k` (<= 0: 3; lssp_solver_set_augk, lssp.cxx:485)
 PC_NON, PC_ILUK, PC_ILUT = 0, 1, 2
 SERIAL, TREE = 0, 1
 
@@ -68,6 +69,8 @@ def lib():
         _lib.orc_solve.restype = _ci
         _lib.orc_solve.argtypes = ([_ci, _ci] + [_vp] * 9 + [_vp, _vp, _cd, _cd, _cd, _ci, _ci, _ci, _ci]
                                    + [_vp, _ci, _vp, _vp])
+        _lib.orc_solve_k.restype = _ci
+        _lib.orc_solve_k.argtypes = _lib.orc_solve.argtypes + [_ci]
         _lib.orc_poisson_nnz.restype = _cl
         _lib.orc_poisson_nnz.argtypes = [_ci, _ci]
         _lib.orc_poisson.argtypes = [_ci, _ci, _vp, _vp, _vp]
@@ -98,7 +101,7 @@ def ref():
         _ref.ref_ilu_free.argtypes = [_vp]
         _ref.ref_solve.restype = _ci
         _ref.ref_solve.argtypes = ([_ci, _ci, _ci, _cd, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
-                                    _cd, _cd, _cd, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp])
+                                    _cd, _cd, _cd, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci])
         _ref.ref_time.restype = _cd
     return _ref
 
@@ -176,15 +179,15 @@ class SolveResult:
 
 
 def solve(solver, A: CSR, b, x0=None, L=None, U=None, rtol=1e-7, atol=1e-7, rbtol=1e-7,
-          maxit=1000, restart=30, mode=SERIAL, nranks=1, trace_cap=200000) -> SolveResult:
+          maxit=1000, restart=30, mode=SERIAL, nranks=1, trace_cap=200000, aug_k=3) -> SolveResult:
     x = np.zeros(A.n) if x0 is None else np.array(x0, dtype=np.float64)
     tr = np.zeros(trace_cap)
     tl, res = ctypes.c_int(), ctypes.c_double()
-    it = lib().orc_solve(solver, A.n, _ptr(A.Ap), _ptr(A.Aj), _ptr(A.Ax),
-                         _ptr(L.Ap) if L else None, _ptr(L.Aj) if L else None, _ptr(L.Ax) if L else None,
-                         _ptr(U.Ap) if U else None, _ptr(U.Aj) if U else None, _ptr(U.Ax) if U else None,
-                         _ptr(x), _ptr(b), rtol, atol, rbtol, maxit, restart, mode, nranks,
-                         _ptr(tr), trace_cap, ctypes.byref(tl), ctypes.byref(res))
+    it = lib().orc_solve_k(solver, A.n, _ptr(A.Ap), _ptr(A.Aj), _ptr(A.Ax),
+                           _ptr(L.Ap) if L else None, _ptr(L.Aj) if L else None, _ptr(L.Ax) if L else None,
+                           _ptr(U.Ap) if U else None, _ptr(U.Aj) if U else None, _ptr(U.Ax) if U else None,
+                           _ptr(x), _ptr(b), rtol, atol, rbtol, maxit, restart, mode, nranks,
+                           _ptr(tr), trace_cap, ctypes.byref(tl), ctypes.byref(res), aug_k)
     return SolveResult(it, res.value, x, tr[: min(tl.value, trace_cap)].copy())
 
 
@@ -224,14 +227,16 @@ def ref_ilu_apply(A: CSR, rhs, kind="iluk", level=0, tol=1e-3, p=-1):
 
 
 def ref_solve(solver, A: CSR, b, pc=PC_NON, level=0, ilut_tol=1e-3, ilut_p=-1, x0=None,
-              rtol=1e-7, atol=1e-7, rbtol=1e-7, maxit=1000, restart=30, trace_cap=200000) -> SolveResult:
+              rtol=1e-7, atol=1e-7, rbtol=1e-7, maxit=1000, restart=30, trace_cap=200000,
+              aug_k=0) -> SolveResult:
+    """aug_k > 0: lssp_solver_set_augk(aug_k); else the reference's own default stays"""
     x = np.zeros(A.n) if x0 is None else np.array(x0, dtype=np.float64)
     tr = np.zeros(trace_cap)
     tl, res, ts, tv = ctypes.c_int(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
     it = ref().ref_solve(solver, pc, level, ilut_tol, ilut_p, A.n, _ptr(A.Ap), _ptr(A.Aj), _ptr(A.Ax),
                          _ptr(x), _ptr(np.ascontiguousarray(b, dtype=np.float64)), rtol, atol, rbtol,
                          maxit, restart, _ptr(tr), trace_cap, ctypes.byref(tl), ctypes.byref(res),
-                         ctypes.byref(ts), ctypes.byref(tv))
+                         ctypes.byref(ts), ctypes.byref(tv), aug_k)
     return SolveResult(it, res.value, x, tr[: min(tl.value, trace_cap)].copy(), ts.value, tv.value)
 
 
@@ -249,7 +254,7 @@ def ref_bj(A: CSR, nblk: int):
 
 
 def ref_solve_bj(solver, A: CSR, b, nblk: int, x0=None, rtol=1e-7, atol=1e-7, rbtol=1e-7,
-                 maxit=1000, restart=30, trace_cap=200000) -> SolveResult:
+                 maxit=1000, restart=30, trace_cap=200000, aug_k=0) -> SolveResult:
     """Solve with block-Jacobi ILU(0) plugged in through LSSP_PC_USER."""
     R = ref()
     R.ref_bj_create.restype = _vp
@@ -257,7 +262,7 @@ def ref_solve_bj(solver, A: CSR, b, nblk: int, x0=None, rtol=1e-7, atol=1e-7, rb
     R.ref_bj_free.argtypes = [_vp]
     R.ref_solve_bj.restype = _ci
     R.ref_solve_bj.argtypes = [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _ci, _ci,
-                               _vp, _ci, _vp, _vp]
+                               _vp, _ci, _vp, _vp, _ci]
     h = R.ref_bj_create(A.n, _ptr(A.Ap), _ptr(A.Aj), _ptr(A.Ax), nblk)
     try:
         x = np.zeros(A.n) if x0 is None else np.array(x0, dtype=np.float64)
@@ -265,7 +270,7 @@ def ref_solve_bj(solver, A: CSR, b, nblk: int, x0=None, rtol=1e-7, atol=1e-7, rb
         tl, res = ctypes.c_int(), ctypes.c_double()
         it = R.ref_solve_bj(h, solver, A.n, _ptr(A.Ap), _ptr(A.Aj), _ptr(A.Ax), _ptr(x),
                             _ptr(np.ascontiguousarray(b, dtype=np.float64)), rtol, atol, rbtol, maxit,
-                            restart, _ptr(tr), trace_cap, ctypes.byref(tl), ctypes.byref(res))
+                            restart, _ptr(tr), trace_cap, ctypes.byref(tl), ctypes.byref(res), aug_k)
         return SolveResult(it, res.value, x, tr[: min(tl.value, trace_cap)].copy())
     finally:
         R.ref_bj_free(h)

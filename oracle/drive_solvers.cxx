@@ -4,13 +4,13 @@
 // 61-127 call sequence: lssp_solver_create -> set_* -> lssp_solver_assemble ->
 // lssp_solver_solve), parameterised by solver, PC and grid, so the same
 // program can be linked twice (oracle/Makefile `exam`):
-//   _ref/drive_ref  against the reference alone (the checker);
-//   _ref/drive_amd  with integration/amd_backend.cxx wrapping the drivers onto
-//                   lssp_amd (tests/test_gpu_integration.py).
+//   _ref/drive_solvers_ref  against the reference alone (the checker);
+//   _ref/drive_solvers_amd  with integration/amd_backend.cxx wrapping the drivers
+//                           onto lssp_amd (tests/test_gpu_integration.py).
 // It prints the iteration count, the residual and digests of x in %.17e, so
 // the two binaries' outputs can be compared as strings.
 //
-// usage: drive_solvers SOLVER PC LEVEL N MAXIT PARAM [REPEAT]
+// usage: drive_solvers SOLVER PC LEVEL N MAXIT PARAM [REPEAT [AUGK]]
 //   SOLVER  LSSP_SOLVER_TYPE value (type-defs.h:157-178)
 //   PC      0 PC_NON, 1 ILUK (LEVEL), 2 ILUT(1e-4, 20), 3 a user PC (LSSP_PC_USER,
 //           pc.cxx:219-227) whose assemble calls lssp_pc_iluk_assemble (LEVEL)
@@ -21,6 +21,7 @@
 //           2: after the solve, apply the preconditioner directly through the
 //           function pointer, pc.solve(&pc, r, x) and pc.solve(&pc, r, b)
 //           (type-defs.h:103-105) -- two "pcsolve" lines
+//   AUGK    k of LGMRES / RLGMRES (lssp_solver_set_augk); <= 0 or absent: default
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -68,8 +69,8 @@ static void user_ilu_assemble(LSSP_PC &pc, LSSP_SOLVER s)
 
 int main(int argc, char **argv)
 {
-    if (argc != 7 && argc != 8) {
-        fprintf(stderr, "usage: %s SOLVER PC LEVEL N MAXIT PARAM [REPEAT]\n", argv[0]);
+    if (argc < 7 || argc > 9) {
+        fprintf(stderr, "usage: %s SOLVER PC LEVEL N MAXIT PARAM [REPEAT [AUGK]]\n", argv[0]);
         return 2;
     }
     const int sv = atoi(argv[1]), pct = atoi(argv[2]), level = atoi(argv[3]), N = atoi(argv[4]);
@@ -105,7 +106,9 @@ int main(int argc, char **argv)
         else if (sv == LSSP_SOLVER_IDRS) lssp_solver_set_idrs(solver, param);
         else lssp_solver_set_restart(solver, param);
     }
-    const int mode = argc == 8 ? atoi(argv[7]) : 0;
+    const int augk = argc == 9 ? atoi(argv[8]) : 0;
+    if (augk > 0 && (sv == LSSP_SOLVER_LGMRES || sv == LSSP_SOLVER_RLGMRES)) lssp_solver_set_augk(solver, augk);
+    const int mode = argc >= 8 ? atoi(argv[7]) : 0;
     const bool repeat = mode == 1;
     auto report = [&]() {
         double s1 = 0, s2 = 0;

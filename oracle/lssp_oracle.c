@@ -33,6 +33,7 @@ static const double ZERO_DIAG_TOL = 1e-10;
 static const double BREAKDOWN = 1e-40;
 static const int DEF_MAXIT = 1000;
 static const int DEF_RESTART = 50;
+static const int DEF_AUG_K = 3;
 static const double DEF_TOL = 1e-7;
 
 typedef struct {
@@ -841,7 +842,7 @@ EXPORT void orc_ilu_free(void *hp)
 /* Krylov drivers                                                           */
 /* ------------------------------------------------------------------------ */
 
-enum { SOLVER_GMRES = 0, SOLVER_LGMRES = 1, SOLVER_RGMRES = 2, SOLVER_BICGSTAB = 4, SOLVER_CG = 7 }; /* type-defs.h:157-178 */
+enum { SOLVER_GMRES = 0, SOLVER_LGMRES = 1, SOLVER_RGMRES = 2, SOLVER_RLGMRES = 3, SOLVER_BICGSTAB = 4, SOLVER_CG = 7 }; /* type-defs.h:157-178 */
 
 typedef struct {
     const csr_t *A;
@@ -1208,15 +1209,17 @@ done:
 }
 
 /* solver-lgmres.cxx:12-312: LGMRES(m, k), left preconditioned, augmented with
- * the last k corrections (k = LSSP_AUG_K = 3, lssp.cxx:6).  Quirks kept: true
+ * the last k corrections (k <= 0: LSSP_AUG_K = 3, lssp.cxx:6; the reference's
+ * setter refuses k <= 0 and its driver defaults k < 0).  Quirks kept: true
  * divisions for v_0 and v_{i+1}; the solve uses kk = i columns; the x update
  * reads y[m + i] for the first min(cycle, k) z vectors whenever kk > m (y
  * persists across cycles; the reference mallocs it uninitialised, zero here). */
 static int lgmres(ctx_t *c, double *x, const double *b, double tol_rel, double tol_abs,
-                  double tol_rb, int maxit, int mk, double *res_out)
+                  double tol_rb, int maxit, int mk, int auk, double *res_out)
 {
     const csr_t *A = c->A;
-    int n = A->nrows, inner = 0, outer = 0, auk = 3;
+    int n = A->nrows, inner = 0, outer = 0;
+    if (auk <= 0) auk = DEF_AUG_K;
     if (mk < 0) mk = DEF_RESTART;
     if (maxit <= 0) maxit = DEF_MAXIT;
     if (tol_abs < 0) tol_abs = DEF_TOL;
@@ -1314,6 +1317,122 @@ static int lgmres(ctx_t *c, double *x, const double *b, double tol_rel, double t
         beta = tnorm(c, rg);
         if (beta <= tol) break;
         gstol = rtol * gs_norm / (beta / err_rel) * 0.5;
+        outer++;
+    }
+#undef HG
+done:
+    *res_out = beta;
+    free(wj); free(rg);
+    for (int i = 0; i < mmax; i++) free(v[i]);
+    for (int i = 0; i < auk; i++) free(z[i]);
+    free(v); free(z); free(gg); free(ym); free(H); free(cs); free(sn);
+    return inner;
+}
+
+/* solver-lgmres.cxx:313-604: right-preconditioned LGMRES(m, k).  The Arnoldi
+ * step is gmres_r's (v_0 = rg * (1 / beta), v_{i+1} = w * (1 / h), the residual
+ * reported is the Givens estimate); the cycle's width grows by one column per
+ * cycle up to m + k, and column i >= m is A M^-1 z_{i-m}.  Quirks kept: the
+ * solve uses kk = i columns, so an exit at beta <= tol drops the last one; the
+ * back substitution leaves i at -1, so the test at :516 always holds and the
+ * update sums the kk BASIS vectors only, also when kk > m; x += M^-1 rg and
+ * z[outer % k] = rg, both only when kk > 0; z reads as zero until set (the
+ * golden runs use zero-initialising malloc, oracle/ref_shim.cxx). */
+static int lgmres_r(ctx_t *c, double *x, const double *b, double tol_rel, double tol_abs,
+                    double tol_rb, int maxit, int mk, int auk, double *res_out)
+{
+    const csr_t *A = c->A;
+    int n = A->nrows, inner = 0, outer = 0;
+    if (auk <= 0) auk = DEF_AUG_K;
+    if (mk < 0) mk = DEF_RESTART;
+    if (maxit <= 0) maxit = DEF_MAXIT;
+    if (tol_abs < 0) tol_abs = DEF_TOL;
+    if (tol_rel < 0) tol_rel = DEF_TOL;
+    if (tol_rb < 0) tol_rb = DEF_TOL;
+    int mmax = mk + auk;
+    size_t bytes = sizeof(double) * (size_t)n;
+    double *wj = malloc(bytes), *rg = malloc(bytes);
+    double **v = malloc(sizeof(double *) * (size_t)mmax);
+    for (int i = 0; i < mmax; i++) v[i] = malloc(bytes);
+    double **z = malloc(sizeof(double *) * (size_t)auk);
+    for (int i = 0; i < auk; i++) z[i] = calloc((size_t)(n > 0 ? n : 1), sizeof(double));
+    double *gg = malloc(sizeof(double) * (size_t)(mmax + 1)), *ym = calloc((size_t)mmax, sizeof(double));
+    double *H = malloc(sizeof(double) * (size_t)(mmax + 1) * (size_t)mmax);
+    double *cs = malloc(sizeof(double) * (size_t)mmax), *sn = malloc(sizeof(double) * (size_t)mmax);
+#define HG(r, col) H[(size_t)(r) * (size_t)mmax + (size_t)(col)]
+    double tol = 0, err_rel = 0, beta;
+
+    double bnorm = tnorm(c, b);
+    tol_rb *= bnorm;
+    mv_amxpbyz(-1, A, x, 1, b, rg);
+    beta = tnorm(c, rg);
+    if (beta <= tol_abs) goto done;
+    err_rel = beta;
+    tol = tol_rel * err_rel;
+    if (tol < tol_abs) tol = tol_abs;
+    if (tol < tol_rb) tol = tol_rb;
+
+    while (inner < maxit) {
+        int i, kk;
+        int m = outer < auk ? mk + outer : mk + auk;
+        for (kk = 1; kk <= m; kk++) gg[kk] = 0;
+        for (size_t q = 0; q < (size_t)(mmax + 1) * (size_t)mmax; q++) H[q] = 0;
+        gg[0] = beta = tnorm(c, rg);
+        {
+            double a = 1 / beta;
+            for (int q = 0; q < n; q++) v[0][q] = rg[q] * a; /* vector.cxx:86-95 */
+        }
+        for (i = 0; i < m && inner < maxit; i++) {
+            double h;
+            inner++;
+            pc_apply(c, rg, i < mk ? v[i] : z[i - mk]);
+            mv_mxy(A, rg, wj);
+            for (int j = 0; j <= i; j++) {
+                h = tdot(c, wj, v[j]);
+                for (int q = 0; q < n; q++) wj[q] = wj[q] * 1 + v[j][q] * (-h);
+                HG(j, i) = h;
+            }
+            h = tnorm(c, wj);
+            HG(i + 1, i) = h;
+            if (fabs(h) <= BREAKDOWN) {
+                i--;
+                break;
+            } else if (i + 1 < m) {
+                double a = 1 / h;
+                for (int q = 0; q < n; q++) v[i + 1][q] = wj[q] * a;
+            }
+            for (int j = 0; j < i; j++) {
+                double h1 = cs[j] * HG(j, i) + sn[j] * HG(j + 1, i);
+                double h2 = -sn[j] * HG(j, i) + cs[j] * HG(j + 1, i);
+                HG(j, i) = h1;
+                HG(j + 1, i) = h2;
+            }
+            double gma = sqrt(HG(i, i) * HG(i, i) + HG(i + 1, i) * HG(i + 1, i));
+            if (fabs(gma) == 0.) gma = 1e-20;
+            cs[i] = HG(i, i) / gma;
+            sn[i] = HG(i + 1, i) / gma;
+            gg[i + 1] = -sn[i] * gg[i];
+            gg[i] = cs[i] * gg[i];
+            HG(i, i) = cs[i] * HG(i, i) + sn[i] * HG(i + 1, i);
+            beta = fabs(gg[i + 1]);
+            if (beta <= tol) break; /* goto solve: i not advanced */
+        }
+        kk = i;
+        for (i = kk - 1; i >= 0; i--) {
+            ym[i] = gg[i] / HG(i, i);
+            for (int j = 0; j < i; j++) gg[j] = gg[j] - ym[i] * HG(j, i);
+        }
+        if (kk > 0) {
+            for (int q = 0; q < n; q++) rg[q] = v[0][q] * ym[0];
+            for (i = 1; i < kk; i++)
+                for (int q = 0; q < n; q++) rg[q] = rg[q] * 1 + v[i][q] * ym[i];
+            pc_apply(c, wj, rg);
+            for (int q = 0; q < n; q++) x[q] = x[q] * 1 + wj[q] * 1;
+            memcpy(z[outer % auk], rg, bytes);
+        }
+        if (beta <= tol) break;
+        mv_amxpbyz(-1, A, x, 1, b, rg);
+        beta = tnorm(c, rg);
         outer++;
     }
 #undef HG
@@ -2232,13 +2351,14 @@ static int l1_solve(ctx_t *c, int solver, double *x, const double *b, double tol
 
 /* Solve A x = b (x holds x0 on entry).  L/U == NULL => PC_NON.
  * trace receives every dot/norm the driver computes, in call order (the same
- * sequence tests/golden records from the reference). */
-EXPORT int orc_solve(int solver, int n, const int *Ap, const int *Aj, const double *Ax,
+ * sequence tests/golden records from the reference).  aug_k: the k of
+ * LGMRES / RLGMRES (<= 0: 3); the other drivers ignore it. */
+EXPORT int orc_solve_k(int solver, int n, const int *Ap, const int *Aj, const double *Ax,
                      const int *Lp, const int *Lj, const double *Lx,
                      const int *Up, const int *Uj, const double *Ux,
                      double *x, const double *b, double tol_rel, double tol_abs, double tol_rb,
                      int maxit, int restart, int red_mode, int nranks,
-                     double *trace, int trace_cap, int *trace_len, double *residual)
+                     double *trace, int trace_cap, int *trace_len, double *residual, int aug_k)
 {
     csr_t A = csr_copy(n, n, Ap, Aj, Ax);
     sort_columns(&A);
@@ -2261,7 +2381,8 @@ EXPORT int orc_solve(int solver, int n, const int *Ap, const int *Aj, const doub
     case SOLVER_CG: it = cg(&c, x, b, tol_rel, tol_abs, tol_rb, maxit, &res); break;
     case SOLVER_GMRES: it = gmres(&c, x, b, tol_rel, tol_abs, tol_rb, maxit, restart, &res); break;
     case SOLVER_RGMRES: it = gmres_r(&c, x, b, tol_rel, tol_abs, tol_rb, maxit, restart, &res); break;
-    case SOLVER_LGMRES: it = lgmres(&c, x, b, tol_rel, tol_abs, tol_rb, maxit, restart, &res); break;
+    case SOLVER_LGMRES: it = lgmres(&c, x, b, tol_rel, tol_abs, tol_rb, maxit, restart, aug_k, &res); break;
+    case SOLVER_RLGMRES: it = lgmres_r(&c, x, b, tol_rel, tol_abs, tol_rb, maxit, restart, aug_k, &res); break;
     default: it = l1_solve(&c, solver, x, b, tol_rel, tol_abs, tol_rb, maxit, restart, &res);
     }
     if (trace_len) *trace_len = c.len;
@@ -2269,6 +2390,18 @@ EXPORT int orc_solve(int solver, int n, const int *Ap, const int *Aj, const doub
     free(c.cache);
     csr_free(&A);
     return it;
+}
+
+/* orc_solve_k with the default k */
+EXPORT int orc_solve(int solver, int n, const int *Ap, const int *Aj, const double *Ax,
+                     const int *Lp, const int *Lj, const double *Lx,
+                     const int *Up, const int *Uj, const double *Ux,
+                     double *x, const double *b, double tol_rel, double tol_abs, double tol_rb,
+                     int maxit, int restart, int red_mode, int nranks,
+                     double *trace, int trace_cap, int *trace_len, double *residual)
+{
+    return orc_solve_k(solver, n, Ap, Aj, Ax, Lp, Lj, Lx, Up, Uj, Ux, x, b, tol_rel, tol_abs, tol_rb, maxit,
+                       restart, red_mode, nranks, trace, trace_cap, trace_len, residual, 0);
 }
 
 /* ------------------------------------------------------------------------ */

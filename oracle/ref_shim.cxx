@@ -157,10 +157,11 @@ void ref_ilu_free(void *hp)
 // Full solve through the API.  solver: LSSP_SOLVER_TYPE (0 GMRES, 4 BICGSTAB,
 // 7 CG); pc: 0 none, 1 ILUK, 2 ILUT.  x holds x0 on entry.  Every dot/norm
 // the driver evaluates is appended to trace (up to cap), in call order.
+// aug_k > 0: the k of LGMRES / RLGMRES (lssp_solver_set_augk); else the default.
 int ref_solve(int solver, int pc_type, int level, double ilut_tol, int ilut_p, int n,
               const int *Ap, const int *Aj, const double *Ax, double *x, const double *b,
               double rtol, double atol, double rbtol, int maxit, int restart, double *trace,
-              int cap, int *trace_len, double *residual, double *t_setup, double *t_solve)
+              int cap, int *trace_len, double *residual, double *t_setup, double *t_solve, int aug_k)
 {
     LSSP_SOLVER s;
     LSSP_PC pc;
@@ -185,6 +186,7 @@ int ref_solve(int solver, int pc_type, int level, double ilut_tol, int ilut_p, i
     // BiCGSTAB(l) / IDR(s): l / s ride in `restart` (lssp_solver_set_bgsl / _idrs, lssp.cxx:495-513)
     if (restart > 0 && solver == LSSP_SOLVER_BICGSTABL) lssp_solver_set_bgsl(s, restart);
     if (restart > 0 && solver == LSSP_SOLVER_IDRS) lssp_solver_set_idrs(s, restart);
+    if (aug_k > 0) lssp_solver_set_augk(s, aug_k);
     double t0 = lssp_get_time();
     lssp_solver_assemble(s, A, vview(n, x), vview(n, b), pc);
     double t1 = lssp_get_time();
@@ -298,7 +300,7 @@ extern "C" void ref_bj_free(void *hp)
 extern "C" int ref_solve_bj(void *hp, int solver, int n, const int *Ap, const int *Aj,
                             const double *Ax, double *x, const double *b, double rtol, double atol,
                             double rbtol, int maxit, int restart, double *trace, int cap,
-                            int *trace_len, double *residual)
+                            int *trace_len, double *residual, int aug_k)
 {
     ref_pc *h = (ref_pc *)hp;
     LSSP_SOLVER s;
@@ -318,6 +320,7 @@ extern "C" int ref_solve_bj(void *hp, int solver, int n, const int *Ap, const in
     // BiCGSTAB(l) / IDR(s): l / s ride in `restart` (lssp_solver_set_bgsl / _idrs, lssp.cxx:495-513)
     if (restart > 0 && solver == LSSP_SOLVER_BICGSTABL) lssp_solver_set_bgsl(s, restart);
     if (restart > 0 && solver == LSSP_SOLVER_IDRS) lssp_solver_set_idrs(s, restart);
+    if (aug_k > 0) lssp_solver_set_augk(s, aug_k);
     lssp_solver_assemble(s, A, vview(n, x), vview(n, b), pc);
     g_trace.clear();
     g_trace_on = true;

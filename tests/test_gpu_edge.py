@@ -148,7 +148,11 @@ def test_ilu_degenerate_factors_bitwise_vs_oracle(dev, case):
     assert _same(x.download(), O.ilu_apply(L, U, rhs))
 
 
-@pytest.mark.parametrize("solver", ["BICGSTAB", "CG", "GMRES", "IDRS", "BICGSTABL", "TFQMR"])
+# all 19 drivers.  ILU(0) is exact on both systems, so LGMRES, RGMRES and RLGMRES too meet the
+# breakdown exit at column 0 (i = -1, kk = -1; K_LGM_X unpacks kk as a short)
+@pytest.mark.parametrize("solver", ["BICGSTAB", "CG", "GMRES", "IDRS", "BICGSTABL", "TFQMR", "LGMRES", "RGMRES",
+                                    "RLGMRES", "BICGSAFE", "CGS", "GPBICG", "CR", "CRS", "BICRSTAB", "BICRSAFE",
+                                    "GPBICR", "QMRCGSTAB", "ORTHOMIN"])
 @pytest.mark.parametrize("system", ["1x1", "diagonal"])
 def test_solvers_on_trivial_systems_bitwise_vs_oracle(dev, solver, system):
     import lssp_amd

@@ -55,11 +55,11 @@ def test_exam_drop_in_tree_reduction_converges_alike():
 # ---- every driver through the binding ---------------------------------------
 # oracle/drive_solvers.cxx: an exam.cxx-style caller of the reference API
 # (lssp_solver_create / set_* / assemble / solve) parameterised by solver, PC
-# and grid, linked against the reference alone (drive_ref) and through
-# integration/amd_backend.cxx (drive_amd).  In SERIAL reduction mode the two
+# and grid, linked against the reference alone (drive_solvers_ref) and through
+# integration/amd_backend.cxx (drive_solvers_amd).  In SERIAL reduction mode the two
 # print the same nits, residual and x digests, digit for digit.
-DRV_REF = os.path.join(ROOT, "oracle", "_ref", "drive_ref")
-DRV_AMD = os.path.join(ROOT, "oracle", "_ref", "drive_amd")
+DRV_REF = os.path.join(ROOT, "oracle", "_ref", "drive_solvers_ref")
+DRV_AMD = os.path.join(ROOT, "oracle", "_ref", "drive_solvers_amd")
 ALL_SOLVERS = {"gmres": 0, "lgmres": 1, "gmres_r": 2, "bicgstab": 4, "bicgstabl": 5, "bicgsafe": 6, "cg": 7,
                "cgs": 8, "gpbicg": 9, "cr": 10, "crs": 11, "bicrstab": 12, "bicrsafe": 13, "gpbicr": 14,
                "qmrcgstab": 15, "tfqmr": 16, "orthomin": 17, "idrs": 18}
@@ -84,6 +84,17 @@ def test_every_driver_drop_in_serial_reduction_bitwise(solver, cfg):
     ref = _drive(DRV_REF, args)
     amd = _drive(DRV_AMD, args, LSSP_AMD_REDUCE="serial")
     assert amd == ref
+
+
+def test_lgmres_k_arrives_through_the_binding():
+    """drive_solvers AUGK: lssp_solver_set_augk(2) before the solve.  LGMRES(3, 2) on the
+    unpreconditioned system runs many cycles, so k decides the run; the binding forwards s.aug_k"""
+    args = [str(ALL_SOLVERS["lgmres"]), *DRV_CONFIGS["none"]]
+    ref3 = _drive(DRV_REF, args)
+    ref2 = _drive(DRV_REF, args + ["0", "2"])
+    assert ref2 != ref3  # k = 2 is another run than the default k = 3
+    assert _drive(DRV_AMD, args + ["0", "2"], LSSP_AMD_REDUCE="serial") == ref2
+    assert _drive(DRV_AMD, args, LSSP_AMD_REDUCE="serial") == ref3
 
 
 @pytest.mark.parametrize("solver,pc", [("bicgstab", "iluk0"), ("gmres", "iluk0"), ("cg", "none")])

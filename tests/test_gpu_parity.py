@@ -7,6 +7,7 @@ All comparisons are bitwise except where a test says otherwise:
   * solvers in TREE mode (the fast path) against the oracle restating the same
     canonical reduction order.
 """
+import json
 import os
 
 import numpy as np
@@ -108,7 +109,9 @@ def test_solver_serial_mode_trace_bitwise_vs_reference(dev, c):
     assert matches(c["x"], x.download())
 
 
-TREE_CASES = [c for c in SOLVE if c["mat"].get("N", 0) <= 64 or c["mat"]["type"] == "rand"]
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rlgmres_manifest.json")) as _f:
+    RLGMRES_SOLVE = json.load(_f)["cases"]  # the reference's RLGMRES runs; SERIAL mode: tests/test_gpu_rlgmres.py
+TREE_CASES = [c for c in SOLVE + RLGMRES_SOLVE if c["mat"].get("N", 0) <= 64 or c["mat"]["type"] == "rand"]
 L1_SOLVERS = (O.BICGSAFE, O.CGS, O.GPBICG, O.CR, O.CRS, O.BICRSTAB, O.BICRSAFE, O.GPBICR, O.QMRCGSTAB, O.TFQMR)
 
 

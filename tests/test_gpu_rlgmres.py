@@ -4,9 +4,10 @@ make_golden_rlgmres.py from oracle/_ref/libref.so).
 
 SERIAL reduction mode: nits, residual, every dot / norm of the trace and x are
 bitwise the reference's, as tests/test_gpu_parity.py checks the other drivers.
-TREE mode (the fast path) has no oracle restatement to compare with: it must
-stop where the reference's run stops, within max(1, 5 %) iterations -- the
-bound of tests/test_gpu_refconv.py.
+TREE mode (the fast path): bitwise the oracle's restatement of the driver in the
+same canonical reduction order (oracle/lssp_oracle.c lgmres_r, pinned to these
+fixtures by tests/test_solver_params_cpu.py), and it stops where the reference's
+run stops, within max(1, 5 %) iterations -- the bound of tests/test_gpu_refconv.py.
 """
 import json
 import math
@@ -15,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+import oracle as O
 from golden_util import build_matrix, case_id, fx, matches, vec
 
 pytestmark = pytest.mark.gpu
@@ -86,6 +88,28 @@ def test_rlgmres_tree_mode_stops_with_the_reference(dev, c):
         # opens with norm(rhs), norm(r0)
         tol = max(fx(c["rtol"]) * r.trace[1], fx(c["atol"]), fx(c["rbtol"]) * r.trace[0])
         assert r.residual <= tol
+
+
+@pytest.mark.parametrize("c", CASES, ids=[case_id(c) for c in CASES])
+def test_rlgmres_tree_mode_bitwise_vs_oracle(dev, c):
+    import lssp_amd
+    r, xh = _run(dev, c, lssp_amd.TREE)
+    A = build_matrix(c["mat"])
+    pc = c["pc"]
+    L = U = None
+    if pc["kind"] == "iluk":
+        L, U = O.ilu(A, "iluk", level=pc["level"])
+    elif pc["kind"] == "ilut":
+        L, U = O.ilu(A, "ilut", tol=pc["tol"], p=pc["p"])
+    elif pc["kind"] == "bj":
+        L, U = O.ilu(A, "iluk", level=0, blk=(A.n + pc["nblk"] - 1) // pc["nblk"])
+    x0 = None if c["x0"] is None else vec(c["x0"], A.n)
+    o = O.solve(O.RLGMRES, A, vec(c["b"], A.n), x0=x0, L=L, U=U, rtol=fx(c["rtol"]), atol=fx(c["atol"]),
+                rbtol=fx(c["rbtol"]), maxit=c["maxit"], restart=c["restart"], mode=O.TREE)
+    assert r.nits == o.nits
+    assert r.residual == o.residual
+    assert np.array_equal(r.trace, o.trace)
+    assert np.array_equal(xh, o.x, equal_nan=True)
 
 
 def test_rlgmres_verbose_lines(dev):
