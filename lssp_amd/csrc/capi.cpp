@@ -166,85 +166,6 @@ void parallel_for(long n, const std::function<void(long, long)> &f, long grain)
     for (std::thread &t : th) t.join();
 }
 
-// Diagonal-id column coding of a device CSR (the SpMV's index stream): the
-// distinct offsets col - row are collected per thread in small open-addressing
-// sets and merged; with at most 255 of them (5- / 7- / 27-point stencils, the
-// z-slab halo columns of a distributed stencil) every entry becomes the byte
-// index of its offset in the ascending table.  Rows are summed exactly as
-// before (same entries, same order): only the way the column is found changes.
-namespace {
-struct OffSet {  // DIAG_MAX, DIAG_HS: internal.h (shared with the device build, convert.hip)
-    int key[DIAG_HS];
-    unsigned char used[DIAG_HS] = {};
-    int count = 0;
-    static unsigned slot(int k) { return ((unsigned)k * 2654435761u) >> 22; }  // 10 bits
-    int find(int k) const
-    {
-        for (unsigned h = slot(k);; h = (h + 1) & (DIAG_HS - 1)) {
-            if (!used[h]) return -1;
-            if (key[h] == k) return (int)h;
-        }
-    }
-    bool add(int k)  // false once more than DIAG_MAX distinct keys were seen
-    {
-        unsigned h = slot(k);
-        for (; used[h]; h = (h + 1) & (DIAG_HS - 1))
-            if (key[h] == k) return true;
-        if (count == DIAG_MAX) return false;
-        used[h] = 1;
-        key[h] = k;
-        count++;
-        return true;
-    }
-};
-}  // namespace
-
-int build_diag_ids(lssp_amd_mat *M, const int *Ap, const int *Aj)
-{
-    M->ndiag = 0;
-    const int n = M->nrows;
-    if (M->nnz == 0 || n == 0) return LSSP_AMD_OK;
-    std::mutex mu;
-    OffSet all;
-    std::atomic<bool> too_many{false};
-    parallel_for(n, [&](long lo, long hi) {
-        OffSet mine;
-        for (long i = lo; i < hi && !too_many.load(std::memory_order_relaxed); i++)
-            for (int k = Ap[i]; k < Ap[i + 1]; k++)
-                if (!mine.add(Aj[k] - (int)i)) {
-                    too_many = true;
-                    return;
-                }
-        std::lock_guard<std::mutex> g(mu);
-        for (int h = 0; h < DIAG_HS && !too_many; h++)
-            if (mine.used[h] && !all.add(mine.key[h])) too_many = true;
-    });
-    if (too_many) return LSSP_AMD_OK;
-    std::vector<int> off;
-    for (int h = 0; h < DIAG_HS; h++)
-        if (all.used[h]) off.push_back(all.key[h]);
-    std::sort(off.begin(), off.end());
-    int id_of[DIAG_HS];
-    for (int t = 0; t < (int)off.size(); t++) id_of[all.find(off[t])] = t;
-    // +32: the SpMV stages the byte stream with 16-byte loads that may touch one
-    // vector past the last entry
-    std::vector<uint8_t> ad((size_t)M->nnz + 32, 0);
-    parallel_for(n, [&](long lo, long hi) {
-        for (long i = lo; i < hi; i++)
-            for (int k = Ap[i]; k < Ap[i + 1]; k++) ad[k] = (uint8_t)id_of[all.find(Aj[k] - (int)i)];
-    });
-    LSSP_HIP(hipMalloc(&M->Ad, ad.size()));
-    LSSP_HIP(hipMalloc(&M->d_off, sizeof(int) * off.size()));
-    LSSP_HIP(hipMemcpy(M->Ad, ad.data(), ad.size(), hipMemcpyHostToDevice));
-    LSSP_HIP(hipMemcpy(M->d_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
-    M->aux_bytes += (long long)ad.size() + (long long)sizeof(int) * (long long)off.size();
-    M->ndiag = (int)off.size();
-    M->max_off = 0;
-    for (int o : off) M->max_off = std::max(M->max_off, std::abs(o));
-    if (M->nhalo == 0) M->max_off_int = M->max_off;  // (distributed: set over the halo-free chunks at upload)
-    return LSSP_AMD_OK;
-}
-
 // The x spans of the 1024-row blocks of k_spmv_win (kernels.hip), for matrices
 // the diagonal-id coding does not cover (more than 255 offsets) whose rows
 // nevertheless stay near the diagonal (locally renumbered meshes: config 5).
@@ -499,9 +420,7 @@ static int upload_csr(lssp_amd_mat *M, const int *Ap, const int *Aj, const doubl
         LSSP_HIP(hipMemcpy(M->Aj, Aj, sizeof(int) * M->nnz, hipMemcpyHostToDevice));
         LSSP_HIP(hipMemcpy(M->Ax, Ax, sizeof(double) * M->nnz, hipMemcpyHostToDevice));
     }
-    LSSP_TRY(build_diag_ids(M, Ap, Aj));
-    LSSP_TRY(build_row_codes(M->ctx, M));
-    LSSP_TRY(build_val_codes(M->ctx, M));
+    LSSP_TRY(build_codings(M->ctx, M));  // from the copy in HBM (convert.hip)
     return build_windows(M, Ap, Aj, Ax);
 }
 

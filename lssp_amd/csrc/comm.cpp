@@ -554,8 +554,9 @@ int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal
                   dev_ok(hipMemcpy(M->Ax, Ax, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice))));
     if (!ok) (void)hipGetLastError();  // clear the sticky error of a failed allocation
     LSSP_TRY(agree_status(c, ok ? LSSP_AMD_OK : LSSP_AMD_ENOMEM));
-    LSSP_TRY(agree_status(c, build_diag_ids(M, Ap, lj.data())));  // the SpMV's column coding (capi.cpp)
-    LSSP_TRY(agree_status(c, build_row_codes(c, M)));              // and its row coding (convert.hip)
+    // the SpMV's codings (convert.hip), each layer's status agreed on.  max_off_int
+    // stays as set above when there are halo columns, and there are no value codes
+    LSSP_TRY(build_codings(c, M, agree_status));
     guard.m = nullptr;
     *out = M;
     return LSSP_AMD_OK;

@@ -23,7 +23,8 @@
 // _bcsr_is_sorted / _sort_column / _adjust_zero_diag / _get_block_diag
 // (matrix-utils.cxx:217-279, :387-698) on device arrays, and
 // lssp_amd_mat_from_device, which builds the handle lssp_amd_mat_upload
-// (capi.cpp) builds, offset-id coding included, from a CSR in HBM.
+// (capi.cpp) builds from a CSR in HBM; and the SpMV's codings of every
+// handle (build_codings: offset ids, row codes, value codes).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -480,132 +481,70 @@ __global__ __launch_bounds__(CT) void k_bd_fill(long n, int blk, const int *__re
     }
 }
 
-// ---- the SpMV's offset-id coding built on the device (build_diag_ids, capi.cpp) --
-using lssp_amd::DIAG_HS;
+// ---- the SpMV's codings: offset ids (Ad), row codes (Ac), value codes (Av) ----
+// Each layer replaces something the product streams by a byte that indexes a
+// table of at most 256 distinct keys: an entry's col - row, a row's pattern of
+// offset ids, a row's pattern and values.  The three are built the same way: a
+// kernel collects the distinct keys in an open-addressing set (k_collect), the
+// host sorts them into the table (collect_keys), a second kernel bisects the
+// table for every key and writes the byte.  A layer differs in its key type,
+// in how a row yields its keys and in how many keys it admits: its policy
+// (OffKeys, PatKeys, ValKeys).
 using lssp_amd::DIAG_MAX;
+using lssp_amd::ROWPAT_LEN;
+using lssp_amd::ROWPAT_MAX;
+using lssp_amd::ROWVAL_MAX;
+typedef unsigned long long pat_t;
+constexpr int SET_HS = 1024;       // hash slots of every key set
+constexpr int SET_MAX = 256;       // the most keys a layer admits
 constexpr int OFF_EMPTY = INT32_MIN;  // no col - row: columns are >= 0 and rows < INT32_MAX
-// the device-wide set: DIAG_HS hash slots, the number of distinct offsets
-// seen, the overflow flag (a 256th distinct offset), the offsets in arrival order
-constexpr int G_COUNT = DIAG_HS, G_OVER = DIAG_HS + 1, G_LIST = DIAG_HS + 2, G_SIZE = G_LIST + DIAG_MAX;
+constexpr pat_t PAT_EMPTY = ~0ull;    // eight entries of id 254: such a row leaves the matrix uncoded
 
-__device__ __forceinline__ unsigned off_slot(int k) { return ((unsigned)k * 2654435761u) >> 22; }  // 10 bits
+__device__ __forceinline__ unsigned key_slot(int k) { return ((unsigned)k * 2654435761u) >> 22; }  // 10 bits
+__device__ __forceinline__ unsigned key_slot(pat_t k) { return (unsigned)((k * 0x9E3779B97F4A7C15ull) >> 54); }  // 10 bits
 
-__global__ __launch_bounds__(CT) void k_off_init(int *__restrict__ g)
+// the device-wide set of a layer: the hash slots, then what the host fetches:
+// the keys in arrival order, the row that brought each (layers with a payload),
+// the number of distinct keys seen and the flag of a matrix the layer refuses
+// (one key too many, or a row that cannot be coded)
+template <class K>
+struct KeySet {
+    K slot[SET_HS];
+    struct Found {
+        K list[SET_MAX];
+        int row[SET_MAX];
+        int count, over;
+    } found;
+};
+
+template <class K, K EMPTY>
+__global__ __launch_bounds__(CT) void k_set_init(KeySet<K> *__restrict__ g)
 {
-    for (int t = threadIdx.x; t < G_SIZE; t += CT) g[t] = t < DIAG_HS ? OFF_EMPTY : 0;
+    for (int t = threadIdx.x; t < SET_HS; t += CT) g->slot[t] = EMPTY;
+    for (int t = threadIdx.x; t < SET_MAX; t += CT) g->found.list[t] = 0, g->found.row[t] = 0;
+    if (threadIdx.x == 0) g->found.count = g->found.over = 0;
 }
 
-// k into the open-addressing set tab; true when this call claimed its slot.
+// k into the open-addressing set tab of HS slots; the slot this call claimed,
+// or -1 (the key was there, or the set takes no more).
 // A slot is READ first, so a key already present costs no atomic (a stencil's
 // 7 offsets are there after the first rows).  Slots only ever fill, and every
 // inserter of k walks the same probe sequence, so k lands in one slot only.
-// *full (more than DIAG_MAX claims) stops further claims: the set never fills up
-__device__ __forceinline__ bool off_insert(int *tab, const int *full, int k)
+// *full (more than BOUND claims) stops further claims: the set never fills up
+template <class K, int HS, K EMPTY, int BOUND>
+__device__ __forceinline__ int set_insert(K *tab, const int *full, K k)
 {
-    unsigned h = off_slot(k);
-    for (int p = 0; p < DIAG_HS; p++, h = (h + 1) & (DIAG_HS - 1)) {
-        int cur = *(volatile int *)(tab + h);
-        if (cur == k) return false;
-        if (cur != OFF_EMPTY) continue;
-        if (*(volatile const int *)full > DIAG_MAX) return false;
-        int old = atomicCAS(tab + h, OFF_EMPTY, k);
-        if (old == OFF_EMPTY) return true;
-        if (old == k) return false;
+    unsigned h = key_slot(k);
+    for (int p = 0; p < HS; p++, h = (h + 1) & (HS - 1)) {
+        K cur = *(volatile K *)(tab + h);
+        if (cur == k) return -1;
+        if (cur != EMPTY) continue;
+        if (*(volatile const int *)full > BOUND) return -1;
+        K old = atomicCAS(tab + h, EMPTY, k);
+        if (old == EMPTY) return (int)h;
+        if (old == k) return -1;
     }
-    return false;
-}
-
-// distinct col - row of all entries: each block collects its own in an LDS
-// set (70 M entries hit 7 keys: LDS reads, no global traffic), then merges
-// that set into the device-wide one
-__global__ __launch_bounds__(CT) void k_off_collect(long nrows, const int *__restrict__ Ap,
-                                                    const int *__restrict__ Aj, int *__restrict__ g)
-{
-    __shared__ int tab[DIAG_HS];
-    __shared__ int cnt;
-    for (int t = threadIdx.x; t < DIAG_HS; t += CT) tab[t] = OFF_EMPTY;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    GRID_STRIDE(i, nrows)
-    {
-        if (*(volatile int *)&cnt > DIAG_MAX || *(volatile int *)(g + G_OVER)) break;
-        int e = Ap[i + 1];
-        for (int k = Ap[i]; k < e; k++)
-            if (off_insert(tab, &cnt, Aj[k] - (int)i)) atomicAdd(&cnt, 1);
-    }
-    __syncthreads();
-    if (cnt > DIAG_MAX) {
-        if (threadIdx.x == 0) atomicOr(g + G_OVER, 1);
-        return;
-    }
-    for (int t = threadIdx.x; t < DIAG_HS; t += CT) {
-        int k = tab[t];
-        if (k == OFF_EMPTY || !off_insert(g, g + G_COUNT, k)) continue;
-        int at = atomicAdd(g + G_COUNT, 1);
-        if (at < DIAG_MAX)
-            g[G_LIST + at] = k;
-        else
-            atomicOr(g + G_OVER, 1);
-    }
-}
-
-// Ad[k] = index of col - row in the ascending table off[0, nd)
-__global__ __launch_bounds__(CT) void k_off_ids(long nrows, const int *__restrict__ Ap, const int *__restrict__ Aj,
-                                                const int *__restrict__ off, int nd, uint8_t *__restrict__ Ad)
-{
-    __shared__ int tab[DIAG_MAX + 1];
-    for (int t = threadIdx.x; t < nd; t += CT) tab[t] = off[t];
-    __syncthreads();
-    GRID_STRIDE(i, nrows)
-    {
-        int e = Ap[i + 1];
-        for (int k = Ap[i]; k < e; k++) {
-            int o = Aj[k] - (int)i, lo = 0, hi = nd - 1;  // o is in the table by construction
-            while (lo < hi) {
-                int mid = (lo + hi) >> 1;
-                if (tab[mid] < o)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            Ad[k] = (uint8_t)lo;
-        }
-    }
-}
-
-// ---- the SpMV's row coding (lssp_amd_mat::Ac), from the resident Ap and Ad ----
-using lssp_amd::ROWPAT_LEN;
-using lssp_amd::ROWPAT_MAX;
-typedef unsigned long long pat_t;
-constexpr pat_t PAT_EMPTY = ~0ull;  // eight entries of id 254: such a row leaves the matrix uncoded
-constexpr int PAT_HS = 1024;        // hash slots of the pattern sets
-// the device-wide set's counters: distinct patterns seen, the flag of a matrix
-// that cannot be coded; its keys: PAT_HS hash slots, then the patterns in arrival order
-constexpr int P_COUNT = 0, P_OVER = 1;
-
-__device__ __forceinline__ unsigned pat_slot(pat_t k) { return (unsigned)((k * 0x9E3779B97F4A7C15ull) >> 54); }  // 10 bits
-
-__global__ __launch_bounds__(CT) void k_pat_init(pat_t *__restrict__ gk, int *__restrict__ gi)
-{
-    for (int t = threadIdx.x; t < PAT_HS + ROWPAT_MAX; t += CT) gk[t] = t < PAT_HS ? PAT_EMPTY : 0;
-    if (threadIdx.x < 2) gi[threadIdx.x] = 0;
-}
-
-// off_insert for 64-bit pattern keys; *full counts the claims, more than
-// ROWPAT_MAX of them stop further claims
-__device__ __forceinline__ bool pat_insert(pat_t *tab, const int *full, pat_t k)
-{
-    unsigned h = pat_slot(k);
-    for (int p = 0; p < PAT_HS; p++, h = (h + 1) & (PAT_HS - 1)) {
-        pat_t cur = *(volatile pat_t *)(tab + h);
-        if (cur == k) return false;
-        if (cur != PAT_EMPTY) continue;
-        if (*(volatile const int *)full > ROWPAT_MAX) return false;
-        pat_t old = atomicCAS(tab + h, PAT_EMPTY, k);
-        if (old == PAT_EMPTY) return true;
-        if (old == k) return false;
-    }
-    return false;
+    return -1;
 }
 
 // a row's pattern key: byte k = Ad of its entry k, plus 1
@@ -616,77 +555,13 @@ __device__ __forceinline__ pat_t pat_key(const uint8_t *__restrict__ Ad, int b, 
     return key;
 }
 
-// distinct row patterns, collected as k_off_collect collects offsets (10 M
-// rows hit 27 keys); a row of more than ROWPAT_LEN entries raises P_OVER
-__global__ __launch_bounds__(CT) void k_pat_collect(long nrows, const int *__restrict__ Ap,
-                                                    const uint8_t *__restrict__ Ad, pat_t *__restrict__ gk,
-                                                    int *__restrict__ gi)
-{
-    __shared__ pat_t tab[PAT_HS];
-    __shared__ int cnt;
-    for (int t = threadIdx.x; t < PAT_HS; t += CT) tab[t] = PAT_EMPTY;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    GRID_STRIDE(i, nrows)
-    {
-        if (*(volatile int *)&cnt > ROWPAT_MAX || *(volatile int *)(gi + P_OVER)) break;
-        const int b = Ap[i], e = Ap[i + 1];
-        const pat_t key = e - b <= ROWPAT_LEN ? pat_key(Ad, b, e) : PAT_EMPTY;
-        if (key == PAT_EMPTY) {
-            atomicOr(gi + P_OVER, 1);
-            break;
-        }
-        if (pat_insert(tab, &cnt, key)) atomicAdd(&cnt, 1);
-    }
-    __syncthreads();
-    if (cnt > ROWPAT_MAX) {
-        if (threadIdx.x == 0) atomicOr(gi + P_OVER, 1);
-        return;
-    }
-    for (int t = threadIdx.x; t < PAT_HS; t += CT) {
-        pat_t k = tab[t];
-        if (k == PAT_EMPTY || !pat_insert(gk, gi + P_COUNT, k)) continue;
-        int at = atomicAdd(gi + P_COUNT, 1);
-        if (at < ROWPAT_MAX)
-            gk[PAT_HS + at] = k;
-        else
-            atomicOr(gi + P_OVER, 1);
-    }
-}
-
-// Ac[i] = index of row i's key in the ascending table pat[0, np)
-__global__ __launch_bounds__(CT) void k_pat_codes(long nrows, const int *__restrict__ Ap,
-                                                  const uint8_t *__restrict__ Ad, const pat_t *__restrict__ pat,
-                                                  int np, uint8_t *__restrict__ Ac)
-{
-    __shared__ pat_t tab[ROWPAT_MAX];
-    for (int t = threadIdx.x; t < np; t += CT) tab[t] = pat[t];
-    __syncthreads();
-    GRID_STRIDE(i, nrows)
-    {
-        const pat_t key = pat_key(Ad, Ap[i], Ap[i + 1]);  // in the table by construction
-        int lo = 0, hi = np - 1;
-        while (lo < hi) {
-            int mid = (lo + hi) >> 1;
-            if (tab[mid] < key)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        Ac[i] = (uint8_t)lo;
-    }
-}
-
-// ---- the SpMV's value coding (lssp_amd_mat::Av), from the resident Ap, Ac and Ax ----
-// A row's key is its pattern and the bit patterns of its values in CSR order:
-// nine 64-bit words, the pattern key (d_pat[Ac[i]]: ascending with the code)
-// and eight values (+0.0 past the row's length, which the pattern fixes).  The
-// rows are collected by a 64-bit mix of the key in the pattern sets above, each
-// distinct mix with one row that produced it; the table is then those rows'
-// keys, and k_val_codes compares every row with the table in full, so two keys
-// that share a mix leave the matrix uncoded instead of miscoded.
-using lssp_amd::ROWVAL_MAX;
-static_assert(ROWVAL_MAX == ROWPAT_MAX, "the value sets are the pattern sets (pat_insert's bound)");
+// A value row's key is its pattern and the bit patterns of its values in CSR
+// order: nine 64-bit words, the pattern key (d_pat[Ac[i]]: ascending with the
+// code) and eight values (+0.0 past the row's length, which the pattern fixes).
+// The rows are collected by a 64-bit mix of the key, each distinct mix with one
+// row that produced it; the table is then those rows' keys, and k_val_codes
+// compares every row with the table in full, so two keys that share a mix
+// leave the matrix uncoded instead of miscoded.
 constexpr int VAL_WORDS = 1 + ROWPAT_LEN;
 
 __device__ __forceinline__ pat_t val_mix(pat_t h, pat_t v)
@@ -702,63 +577,138 @@ __device__ __forceinline__ pat_t val_hash(unsigned code, const double *__restric
     return h == PAT_EMPTY ? h - 1 : h;
 }
 
-// pat_insert that reports the slot it claimed (-1: the key was there, or the set is full)
-__device__ __forceinline__ int pat_claim(pat_t *tab, const int *full, pat_t k)
-{
-    unsigned h = pat_slot(k);
-    for (int p = 0; p < PAT_HS; p++, h = (h + 1) & (PAT_HS - 1)) {
-        pat_t cur = *(volatile pat_t *)(tab + h);
-        if (cur == k) return -1;
-        if (cur != PAT_EMPTY) continue;
-        if (*(volatile const int *)full > ROWVAL_MAX) return -1;
-        pat_t old = atomicCAS(tab + h, PAT_EMPTY, k);
-        if (old == PAT_EMPTY) return (int)h;
-        if (old == k) return -1;
+// The layers' policies.  row(i, put) hands row i's keys to put(key, at), at
+// being the place of the byte that codes the key (k_codes), and returns false
+// for a row the layer cannot code.  MAX: the keys admitted; ROWS: the set keeps
+// the row that brought each key.
+struct OffKeys {  // col - row of every entry (70 M entries hit 7 keys); coded at the entry
+    typedef int key_t;
+    static constexpr key_t EMPTY = OFF_EMPTY;
+    static constexpr int MAX = DIAG_MAX;
+    static constexpr bool ROWS = false;
+    const int *__restrict__ Ap, *__restrict__ Aj;
+    template <class F>
+    __device__ __forceinline__ bool row(long i, F put) const
+    {
+        const int e = Ap[i + 1];
+        for (int k = Ap[i]; k < e; k++) put(Aj[k] - (int)i, (long)k);
+        return true;
     }
-    return -1;
-}
+};
+struct PatKeys {  // the row's pattern (10 M rows hit 27 keys); more than ROWPAT_LEN entries: not coded
+    typedef pat_t key_t;
+    static constexpr key_t EMPTY = PAT_EMPTY;
+    static constexpr int MAX = ROWPAT_MAX;
+    static constexpr bool ROWS = false;
+    const int *__restrict__ Ap;
+    const uint8_t *__restrict__ Ad;
+    template <class F>
+    __device__ __forceinline__ bool row(long i, F put) const
+    {
+        const int b = Ap[i], e = Ap[i + 1];
+        const pat_t key = e - b <= ROWPAT_LEN ? pat_key(Ad, b, e) : PAT_EMPTY;
+        if (key == PAT_EMPTY) return false;
+        put(key, i);
+        return true;
+    }
+};
+struct ValKeys {  // the mix of the row's pattern code and values, and the row itself
+    typedef pat_t key_t;
+    static constexpr key_t EMPTY = PAT_EMPTY;
+    static constexpr int MAX = ROWVAL_MAX;
+    static constexpr bool ROWS = true;
+    const int *__restrict__ Ap;
+    const uint8_t *__restrict__ Ac;
+    const double *__restrict__ Ax;
+    template <class F>
+    __device__ __forceinline__ bool row(long i, F put) const
+    {
+        put(val_hash(Ac[i], Ax, Ap[i], Ap[i + 1]), i);
+        return true;
+    }
+};
 
-// distinct value rows, as k_pat_collect collects patterns: rep[at] = one row of
-// the at-th distinct mix.  More than ROWVAL_MAX of them raise P_OVER, and every
-// workgroup stops at its next row (a matrix of varying coefficients pays a
-// fraction of one pass)
-__global__ __launch_bounds__(CT) void k_val_collect(long nrows, const int *__restrict__ Ap,
-                                                    const uint8_t *__restrict__ Ac, const double *__restrict__ Ax,
-                                                    pat_t *__restrict__ gk, int *__restrict__ gi,
-                                                    int *__restrict__ rep)
+// the distinct keys of all rows: each block collects its own in an LDS set
+// (LDS reads, no global traffic, for the few keys of a stencil), then merges
+// that set into the device-wide one, where a key new to it joins the list.
+// One key more than P::MAX, or a row that cannot be coded, raises `over`, and
+// every workgroup stops at its next row (a matrix of varying coefficients pays
+// a fraction of one pass)
+template <class P>
+__global__ __launch_bounds__(CT) void k_collect(long nrows, const P p, KeySet<typename P::key_t> *__restrict__ g)
 {
-    __shared__ pat_t tab[PAT_HS];
-    __shared__ int trow[PAT_HS];
+    typedef typename P::key_t K;
+    __shared__ K tab[SET_HS];
+    __shared__ int trow[P::ROWS ? SET_HS : 1];
     __shared__ int cnt;
-    for (int t = threadIdx.x; t < PAT_HS; t += CT) tab[t] = PAT_EMPTY;
+    for (int t = threadIdx.x; t < SET_HS; t += CT) tab[t] = P::EMPTY;
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
     GRID_STRIDE(i, nrows)
     {
-        if (*(volatile int *)&cnt > ROWVAL_MAX || *(volatile int *)(gi + P_OVER)) break;
-        const int at = pat_claim(tab, &cnt, val_hash(Ac[i], Ax, Ap[i], Ap[i + 1]));
-        if (at >= 0) {
-            trow[at] = (int)i;
+        if (*(volatile int *)&cnt > P::MAX || *(volatile int *)&g->found.over) break;
+        const bool coded = p.row(i, [&](K k, long) {
+            const int at = set_insert<K, SET_HS, P::EMPTY, P::MAX>(tab, &cnt, k);
+            if (at < 0) return;
+            if (P::ROWS) trow[at] = (int)i;
             atomicAdd(&cnt, 1);
+        });
+        if (!coded) {
+            atomicOr(&g->found.over, 1);
+            break;
         }
     }
     __syncthreads();
-    if (cnt > ROWVAL_MAX) {
-        if (threadIdx.x == 0) atomicOr(gi + P_OVER, 1);
+    if (cnt > P::MAX) {
+        if (threadIdx.x == 0) atomicOr(&g->found.over, 1);
         return;
     }
-    for (int t = threadIdx.x; t < PAT_HS; t += CT) {
-        pat_t k = tab[t];
-        if (k == PAT_EMPTY || !pat_insert(gk, gi + P_COUNT, k)) continue;
-        int at = atomicAdd(gi + P_COUNT, 1);
-        if (at < ROWVAL_MAX)
-            rep[at] = trow[t];
-        else
-            atomicOr(gi + P_OVER, 1);
+    for (int t = threadIdx.x; t < SET_HS; t += CT) {
+        const K k = tab[t];
+        if (k == P::EMPTY || set_insert<K, SET_HS, P::EMPTY, P::MAX>(g->slot, &g->found.count, k) < 0) continue;
+        const int at = atomicAdd(&g->found.count, 1);
+        if (at < P::MAX) {
+            g->found.list[at] = k;
+            if (P::ROWS) g->found.row[at] = trow[t];
+        } else {
+            atomicOr(&g->found.over, 1);
+        }
     }
 }
 
-// row i's key, word q
+// the first of n ascending table entries that is not below the key: below(m)
+// tells whether entry m is
+template <class F>
+__device__ __forceinline__ int lower_bound(int n, F below)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (below(mid))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// out[at] = index of the key in the ascending table tabg[0, n), for every key
+// of every row (Ad per entry, Ac per row); the keys are in the table by construction
+template <class P>
+__global__ __launch_bounds__(CT) void k_codes(long nrows, const P p, const typename P::key_t *__restrict__ tabg,
+                                              int n, uint8_t *__restrict__ out)
+{
+    typedef typename P::key_t K;
+    __shared__ K tab[SET_MAX];
+    for (int t = threadIdx.x; t < n; t += CT) tab[t] = tabg[t];
+    __syncthreads();
+    GRID_STRIDE(i, nrows)
+    {
+        p.row(i, [&](K key, long at) { out[at] = (uint8_t)lower_bound(n, [&](int m) { return tab[m] < key; }); });
+    }
+}
+
+// row i's value key, word q
 __device__ __forceinline__ pat_t val_word(int q, pat_t pt, const double *__restrict__ Ax, int b, int len)
 {
     if (q == 0) return pt;
@@ -806,14 +756,7 @@ __global__ __launch_bounds__(CT) void k_val_codes(long nrows, const int *__restr
             }
             return r;
         };
-        int lo = 0, hi = nv - 1;
-        while (lo < hi) {
-            int mid = (lo + hi) >> 1;
-            if (cmp(mid) < 0)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
+        const int lo = lower_bound(nv, [&](int c) { return cmp(c) < 0; });
         if (cmp(lo) != 0) atomicOr(bad, 1);
         Av[i] = (uint8_t)lo;
     }
@@ -967,52 +910,122 @@ int bucket(Scratch &S, long nnz, const int *key, int nr, const int *sj, const do
 
 }  // namespace
 
-// The row codes of an offset-coded matrix, from its resident Ap and Ad: one
-// routine for every construction path (upload, distributed upload, device
-// arrays), so the codes, the table and aux_bytes are the same on each.  The
-// patterns are numbered by ascending key, whatever order the rows arrived in.
-int lssp_amd::build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
+namespace {
+
+// A layer's distinct keys over the matrix's rows: keys comes back ascending,
+// or empty when the layer refuses the matrix (one key too many, a row that
+// cannot be coded, no key at all).  *set is the device-wide set in S, whose
+// found.row a layer with a payload reads next.  The table is sorted, so the
+// codes do not depend on the order the keys arrived in.
+template <class P>
+int collect_keys(Scratch &S, long nrows, const P &p, std::vector<typename P::key_t> &keys,
+                 KeySet<typename P::key_t> **set = nullptr)
+{
+    typedef KeySet<typename P::key_t> Set;
+    keys.clear();
+    SCRATCH(g, Set, 1);
+    k_set_init<typename P::key_t, P::EMPTY><<<1, CT, 0, S.s>>>(g);
+    k_collect<P><<<grid_for(nrows), CT, 0, S.s>>>(nrows, p, g);
+    LSSP_HIP(hipGetLastError());
+    typename Set::Found f;
+    LSSP_HIP(hipMemcpyAsync(&f, &g->found, sizeof(f), hipMemcpyDeviceToHost, S.s));
+    LSSP_HIP(hipStreamSynchronize(S.s));
+    if (set) *set = g;
+    if (f.over || f.count > P::MAX || f.count <= 0) return LSSP_AMD_OK;  // not coded
+    keys.assign(f.list, f.list + f.count);
+    std::sort(keys.begin(), keys.end());
+    return LSSP_AMD_OK;
+}
+
+// a stream of n code bytes in HBM.  +32: the SpMV stages a byte stream with
+// 16-byte loads that may touch one vector past the last code
+int byte_stream(hipStream_t s, size_t n, uint8_t **d, size_t *bytes)
+{
+    *bytes = n + 32;
+    LSSP_HIP(hipMalloc(d, *bytes));
+    LSSP_HIP(hipMemsetAsync(*d + n, 0, 32, s));
+    return LSSP_AMD_OK;
+}
+
+// thr[l] = how many of the n ascending pattern keys have at most l entries: a
+// key's length is the place of its highest non-zero byte, so the sorted keys'
+// lengths ascend and a code's length is the number of thresholds it reaches
+void length_thresholds(const pat_t *key, int n, unsigned short *thr)
+{
+    for (int l = 0; l < ROWPAT_LEN; l++) {
+        int shorter = 0;
+        for (int t = 0; t < n; t++) shorter += (key[t] >> (8 * l)) == 0;
+        thr[l] = (unsigned short)shorter;
+    }
+}
+
+// a layer's table in HBM
+template <class K>
+int upload_table(hipStream_t s, const std::vector<K> &tab, K **d)
+{
+    LSSP_HIP(hipMalloc(d, sizeof(K) * tab.size()));
+    LSSP_HIP(hipMemcpyAsync(*d, tab.data(), sizeof(K) * tab.size(), hipMemcpyHostToDevice, s));
+    return LSSP_AMD_OK;
+}
+
+// The offset ids of a CSR in HBM: at most DIAG_MAX distinct col - row (5- / 7- /
+// 27-point stencils, the z-slab halo columns of a distributed stencil), every
+// entry the byte index of its offset in the ascending table.  Rows are summed
+// exactly as before (same entries, same order): only the way the column is
+// found changes.  set_max_off_int: the matrix's halo-free rows are all its rows
+int build_off_ids(lssp_amd_ctx *c, lssp_amd_mat *M, bool set_max_off_int)
+{
+    M->ndiag = 0;
+    if (M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    const OffKeys p{M->Ap, M->Aj};
+    std::vector<int> off;
+    TRY(collect_keys(S, M->nrows, p, off));
+    if (off.empty()) return LSSP_AMD_OK;  // a 256th distinct offset: not coded
+    size_t ad_bytes = 0;
+    TRY(byte_stream(s, (size_t)M->nnz, &M->Ad, &ad_bytes));
+    TRY(upload_table(s, off, &M->d_off));
+    k_codes<OffKeys><<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, p, M->d_off, (int)off.size(), M->Ad);
+    LSSP_HIP(hipGetLastError());
+    LSSP_HIP(hipStreamSynchronize(s));
+    M->aux_bytes += (long long)ad_bytes + (long long)sizeof(int) * (long long)off.size();
+    M->ndiag = (int)off.size();
+    M->max_off = 0;
+    for (int o : off) M->max_off = std::max(M->max_off, std::abs(o));
+    if (set_max_off_int) M->max_off_int = M->max_off;
+    return LSSP_AMD_OK;
+}
+
+// The row codes of an offset-coded matrix, from its resident Ap and Ad: the
+// patterns are numbered by ascending key
+int build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
 {
     M->npat = 0;
     if (M->ndiag == 0 || !M->Ad || M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
     hipStream_t s = c->stream;
     Scratch S(s);
-    SCRATCH(gk, pat_t, PAT_HS + ROWPAT_MAX);
-    SCRATCH(gi, int, 2);
-    k_pat_init<<<1, CT, 0, s>>>(gk, gi);
-    k_pat_collect<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ad, gk, gi);
-    LSSP_HIP(hipGetLastError());
-    int head[2];  // count, flag
-    std::vector<pat_t> pat(ROWPAT_MAX);
-    LSSP_HIP(hipMemcpyAsync(head, gi, sizeof(head), hipMemcpyDeviceToHost, s));
-    LSSP_HIP(hipMemcpyAsync(pat.data(), gk + PAT_HS, sizeof(pat_t) * ROWPAT_MAX, hipMemcpyDeviceToHost, s));
-    LSSP_HIP(hipStreamSynchronize(s));
-    if (head[P_OVER] || head[P_COUNT] > ROWPAT_MAX || head[P_COUNT] <= 0) return LSSP_AMD_OK;  // not row-coded
-    pat.resize(head[P_COUNT]);
-    std::sort(pat.begin(), pat.end());
-    // +32: padded as Ad is
-    const size_t ac_bytes = (size_t)M->nrows + 32;
-    LSSP_HIP(hipMalloc(&M->Ac, ac_bytes));
-    LSSP_HIP(hipMalloc(&M->d_pat, sizeof(pat_t) * pat.size()));
-    LSSP_HIP(hipMemsetAsync(M->Ac + M->nrows, 0, 32, s));
-    LSSP_HIP(hipMemcpyAsync(M->d_pat, pat.data(), sizeof(pat_t) * pat.size(), hipMemcpyHostToDevice, s));
-    k_pat_codes<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ad, M->d_pat, (int)pat.size(), M->Ac);
+    const PatKeys p{M->Ap, M->Ad};
+    std::vector<pat_t> pat;
+    TRY(collect_keys(S, M->nrows, p, pat));
+    if (pat.empty()) return LSSP_AMD_OK;  // a 257th pattern, or a row of more than ROWPAT_LEN entries: not row-coded
+    size_t ac_bytes = 0;
+    TRY(byte_stream(s, (size_t)M->nrows, &M->Ac, &ac_bytes));
+    TRY(upload_table(s, pat, &M->d_pat));
+    k_codes<PatKeys><<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, p, M->d_pat, (int)pat.size(), M->Ac);
     LSSP_HIP(hipGetLastError());
     LSSP_HIP(hipStreamSynchronize(s));
-    // a key's length is the place of its highest non-zero byte, so the sorted keys' lengths ascend
-    for (int l = 0; l < ROWPAT_LEN; l++) {
-        int shorter = 0;
-        for (pat_t k : pat) shorter += (k >> (8 * l)) == 0;  // at most l entries
-        M->pat_thr[l] = (unsigned short)shorter;
-    }
+    length_thresholds(pat.data(), (int)pat.size(), M->pat_thr);
     M->aux_bytes += (long long)ac_bytes + (long long)sizeof(pat_t) * (long long)pat.size();
     M->npat = (int)pat.size();
     return LSSP_AMD_OK;
 }
 
-// The value codes of a row-coded matrix, from its resident Ap, Ac and Ax: one
-// routine for the upload, mat_from_device and every lssp_amd_mat_update_values,
-// which first drops what an earlier call built.  The value rows are numbered
+}  // namespace
+
+// The value codes of a row-coded matrix, from its resident Ap, Ac and Ax:
+// build_codings' last step, and all of lssp_amd_mat_update_values' rebuild,
+// so it first drops what an earlier call built.  The value rows are numbered
 // by ascending key, whatever order the rows arrived in.
 int lssp_amd::build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
 {
@@ -1032,20 +1045,14 @@ int lssp_amd::build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
     if (M->npat == 0 || !M->Ac || M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
     hipStream_t s = c->stream;
     Scratch S(s);
-    SCRATCH(gk, pat_t, PAT_HS + ROWPAT_MAX);
-    SCRATCH(gi, int, 2);
-    SCRATCH(rep, int, ROWVAL_MAX);
     SCRATCH(keys, pat_t, VAL_WORDS * ROWVAL_MAX);
     SCRATCH(bad, int, 1);
-    k_pat_init<<<1, CT, 0, s>>>(gk, gi);
-    k_val_collect<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ac, M->Ax, gk, gi, rep);
-    LSSP_HIP(hipGetLastError());
-    int head[2];  // count, flag
-    LSSP_HIP(hipMemcpyAsync(head, gi, sizeof(head), hipMemcpyDeviceToHost, s));
-    LSSP_HIP(hipStreamSynchronize(s));
-    if (head[P_OVER] || head[P_COUNT] > ROWVAL_MAX || head[P_COUNT] <= 0) return LSSP_AMD_OK;  // not value-coded
-    const int nv = head[P_COUNT];
-    k_val_gather<<<1, CT, 0, s>>>(nv, rep, M->Ap, M->Ac, M->Ax, M->d_pat, keys);
+    std::vector<pat_t> mix;
+    KeySet<pat_t> *set = nullptr;
+    TRY(collect_keys(S, M->nrows, ValKeys{M->Ap, M->Ac, M->Ax}, mix, &set));
+    if (mix.empty()) return LSSP_AMD_OK;  // a 257th distinct value row: not value-coded
+    const int nv = (int)mix.size();
+    k_val_gather<<<1, CT, 0, s>>>(nv, set->found.row, M->Ap, M->Ac, M->Ax, M->d_pat, keys);
     LSSP_HIP(hipGetLastError());
     typedef std::array<pat_t, VAL_WORDS> key_t;
     std::vector<key_t> key(nv);
@@ -1055,13 +1062,10 @@ int lssp_amd::build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
     std::vector<pat_t> tab((size_t)VAL_WORDS * nv);
     for (int q = 0; q < VAL_WORDS; q++)
         for (int t = 0; t < nv; t++) tab[(size_t)q * nv + t] = key[t][q];
-    // +32: padded as Ac is
-    const size_t av_bytes = (size_t)M->nrows + 32;
-    LSSP_HIP(hipMalloc(&M->Av, av_bytes));
-    LSSP_HIP(hipMalloc(&M->d_val, sizeof(pat_t) * tab.size()));
-    LSSP_HIP(hipMemsetAsync(M->Av + M->nrows, 0, 32, s));
+    size_t av_bytes = 0;
+    TRY(byte_stream(s, (size_t)M->nrows, &M->Av, &av_bytes));
+    TRY(upload_table(s, tab, &M->d_val));
     LSSP_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-    LSSP_HIP(hipMemcpyAsync(M->d_val, tab.data(), sizeof(pat_t) * tab.size(), hipMemcpyHostToDevice, s));
     k_val_codes<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Ac, M->Ax, M->d_pat, M->npat, M->d_val, nv,
                                                   M->Av, bad);
     LSSP_HIP(hipGetLastError());
@@ -1084,15 +1088,30 @@ int lssp_amd::build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M)
     }
     LSSP_HIP(hipMalloc(&M->d_voff, sizeof(int) * voff.size()));
     LSSP_HIP(hipMemcpy(M->d_voff, voff.data(), sizeof(int) * voff.size(), hipMemcpyHostToDevice));
-    // as pat_thr: the sorted keys' lengths ascend
-    for (int l = 0; l < ROWPAT_LEN; l++) {
-        int shorter = 0;
-        for (const key_t &k : key) shorter += (k[0] >> (8 * l)) == 0;  // at most l entries
-        M->val_thr[l] = (unsigned short)shorter;
-    }
+    length_thresholds(tab.data(), nv, M->val_thr);  // (the table's first row: the pattern keys)
     M->aux_bytes += (long long)av_bytes + ROW_BYTES * nv;
     M->nval = nv;
     return LSSP_AMD_OK;
+}
+
+// The SpMV's codings of a matrix whose CSR is in HBM, layer on layer: offset
+// ids, then row codes, then value codes.  One routine for every construction
+// path (lssp_amd_mat_upload, lssp_amd_mat_upload_dist, lssp_amd_mat_from_device),
+// so the codes, the tables and aux_bytes are the same on each.  step, when
+// given, sees every layer's status and returns what to go on with
+// (lssp_amd_mat_upload_dist: the status the ranks agree on).
+int lssp_amd::build_codings(lssp_amd_ctx *c, lssp_amd_mat *M, int (*step)(lssp_amd_ctx *, int))
+{
+    auto done = [&](int st) { return step ? step(c, st) : st; };
+    // a matrix with halo columns keeps the max_off_int that the distributed
+    // upload computed over its halo-free chunks
+    TRY(done(build_off_ids(c, M, M->nhalo == 0)));
+    TRY(done(build_row_codes(c, M)));
+    // A distributed matrix is not value-coded and stays on COL_ROW: its
+    // products are split at the halo rows and its values cannot be refreshed,
+    // so the eligibility test would need one more agreement round
+    if (M->dist) return LSSP_AMD_OK;
+    return done(build_val_codes(c, M));
 }
 
 extern "C" {
@@ -1426,41 +1445,6 @@ int lssp_amd_csr_get_block_diag(lssp_amd_ctx *c, int n, int nnz, const int *Ap, 
     return LSSP_AMD_OK;
 }
 
-// build_diag_ids (capi.cpp) for a CSR in HBM: the same table and byte stream
-static int diag_ids_dev(lssp_amd_ctx *c, lssp_amd_mat *M)
-{
-    M->ndiag = 0;
-    if (M->nnz == 0 || M->nrows == 0) return LSSP_AMD_OK;
-    hipStream_t s = c->stream;
-    Scratch S(s);
-    SCRATCH(g, int, G_SIZE);
-    k_off_init<<<1, CT, 0, s>>>(g);
-    k_off_collect<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Aj, g);
-    LSSP_HIP(hipGetLastError());
-    int head[2 + DIAG_MAX];  // count, overflow, the offsets
-    LSSP_HIP(hipMemcpyAsync(head, g + G_COUNT, sizeof(head), hipMemcpyDeviceToHost, s));
-    LSSP_HIP(hipStreamSynchronize(s));
-    if (head[1] || head[0] > DIAG_MAX) return LSSP_AMD_OK;  // a 256th distinct offset: not coded
-    std::vector<int> off(head + 2, head + 2 + head[0]);
-    std::sort(off.begin(), off.end());
-    // +32: see build_diag_ids
-    const size_t ad_bytes = (size_t)M->nnz + 32;
-    LSSP_HIP(hipMalloc(&M->Ad, ad_bytes));
-    LSSP_HIP(hipMalloc(&M->d_off, sizeof(int) * off.size()));
-    LSSP_HIP(hipMemsetAsync(M->Ad + M->nnz, 0, 32, s));
-    LSSP_HIP(hipMemcpyAsync(M->d_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, s));
-    k_off_ids<<<grid_for(M->nrows), CT, 0, s>>>(M->nrows, M->Ap, M->Aj, M->d_off, (int)off.size(), M->Ad);
-    LSSP_HIP(hipGetLastError());
-    LSSP_HIP(hipStreamSynchronize(s));
-    M->aux_bytes += (long long)ad_bytes + (long long)sizeof(int) * (long long)off.size();
-    M->ndiag = (int)off.size();
-    M->max_off = 0;
-    for (int o : off) M->max_off = std::max(M->max_off, std::abs(o));
-    M->max_off_int = M->max_off;
-    TRY(lssp_amd::build_row_codes(c, M));
-    return lssp_amd::build_val_codes(c, M);
-}
-
 // build_windows (capi.cpp) for a CSR in HBM: the span test runs on the device;
 // only a matrix that passes it is downloaded, once, for the host routine that
 // lays out the sliced copy
@@ -1520,7 +1504,7 @@ int lssp_amd_mat_from_device(lssp_amd_ctx *c, int nrows, int ncols, int nnz, con
             LSSP_HIP(hipMemcpyAsync(M->Aj, dAj, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
             LSSP_HIP(hipMemcpyAsync(M->Ax, dAx, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, s));
         }
-        TRY(diag_ids_dev(c, M));
+        TRY(lssp_amd::build_codings(c, M));
         TRY(windows_dev(c, M));
         LSSP_HIP(hipStreamSynchronize(s));
         return LSSP_AMD_OK;

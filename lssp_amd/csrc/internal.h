@@ -402,22 +402,21 @@ namespace lssp_amd {
 
 // ---- kernel launchers (kernels.hip) ------------------------------------------
 enum Epi { EPI_MXY = 0, EPI_AMXY, EPI_AXPBY, EPI_AMX };  // see spmv kernel
-int build_diag_ids(lssp_amd_mat *M, const int *Ap, const int *Aj);
 int build_windows(lssp_amd_mat *M, const int *Ap, const int *Aj, const double *Ax);
 int tune_spmv_streams(lssp_amd_ctx *c, lssp_amd_mat *M);
 constexpr int WIN_ROWS = 1024, WIN_CAP = 16384;
-// diagonal-id coding: at most DIAG_MAX distinct offsets col - row, collected in
-// open-addressing sets of DIAG_HS slots (host: build_diag_ids, capi.cpp;
-// device: lssp_amd_mat_from_device, convert.hip)
-constexpr int DIAG_MAX = 255, DIAG_HS = 1024;
-// row coding of an offset-coded matrix from its resident Ap / Ad (convert.hip):
-// at most ROWPAT_MAX patterns of at most ROWPAT_LEN entries, else npat stays 0
+// The SpMV's codings of a matrix whose Ap / Aj / Ax are in HBM (convert.hip),
+// each layer on the one below: diagonal ids (at most DIAG_MAX distinct offsets
+// col - row, else ndiag stays 0), row codes (at most ROWPAT_MAX patterns of at
+// most ROWPAT_LEN entries, else npat stays 0), value codes (at most ROWVAL_MAX
+// distinct rows, else nval stays 0; not for a distributed matrix).  step:
+// what becomes of each layer's status (lssp_amd_mat_upload_dist's agreement)
+constexpr int DIAG_MAX = 255;
 constexpr int ROWPAT_MAX = 256, ROWPAT_LEN = 8;
-int build_row_codes(lssp_amd_ctx *c, lssp_amd_mat *M);
-// value coding of a row-coded matrix from its resident Ap / Ac / Ax
-// (convert.hip): at most ROWVAL_MAX distinct rows, else nval stays 0.  It
-// first drops the codes the matrix has (lssp_amd_mat_update_values calls it again)
 constexpr int ROWVAL_MAX = 256;
+int build_codings(lssp_amd_ctx *c, lssp_amd_mat *M, int (*step)(lssp_amd_ctx *, int) = nullptr);
+// the value-code layer alone, from the resident Ap / Ac / Ax.  It first drops
+// the codes the matrix has (lssp_amd_mat_update_values calls it again)
 int build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M);
 int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, const double *x,
                 double beta, const double *y, double *z, int nred, const double *w0,

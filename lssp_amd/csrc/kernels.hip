@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <climits>
 #include <vector>
 
@@ -397,56 +398,80 @@ struct SpmvArgs {
 // from a scan of the block's lengths -- a wave scan, the wave totals handed
 // through LDS across the staging barrier -- onto Ap[r0]; only Ax is staged,
 // and every row has at most 8 entries, so a block always fits SPMV_CAP.
-// COL_VAL takes the values too from the row's code (lssp_amd_mat::Av: a table
-// of the matrix's distinct rows, pattern key and 8 values each, of which the
-// workgroup copies the nval live entries to LDS): 1 byte per row and neither
-// Ap nor Ax, so no staging, no scan, and one barrier, behind the table copy.
-// With the value stream gone the kernel is paced by the instructions it issues
-// per entry, so the table is read in its decoded form (lssp_amd_mat::d_voff:
-// a column offset per entry and the row's length) and not through thr / off.
-// A workgroup walks SPMV_VB consecutive blocks of its stream with that one
-// copy: the codes and dot operands of all of them are loaded up front, then
-// all their x gathers are issued, then each block runs its own epilogue and
-// writes its own rows and chunk partial, as a workgroup of its own would.
-// Uniform waves (LSSP_AMD_SPMV_UNI): on a structured grid most waves hold 64
-// rows with one code (216^3: 2/3 of them), so the row's length is the same in
-// every lane.  A wave whose 64 code bytes of a live block are equal and whose
-// rows all lie below nrows takes the length as a scalar (readfirstlane of the
-// LDS word) and resolves it once per block, by a uniform switch: its products
-// are a straight multiply-add chain of exactly that length, with no compare and
-// select per entry (7-entry rows: 14 vector instructions for 36).  Offsets and
-// values it still reads per lane from the LDS table: taking them as scalars too
-// (scalar loads from the global table, gathers from a scalar base) issued a
-// third of the instructions and measured slower -- DESIGN 6.0b.  Same entries,
-// same order, each product rounded on its own: the bits of the per-lane path,
-// which every other wave of the workgroup still takes.
-// LSSP_AMD_SPMV_WAVES: the waves per SIMD the register allocation aims at.  5
-// holds every COL_VAL instance to 96 VGPRs (the three-dot one had 106 and ran
-// 4 waves).  The attribute sits on the whole template and is a lower bound
-// only: it caps the registers at what five waves allow and raises nothing, so
-// the other modes' instances (under 48 VGPRs: 6 to 8 waves) compile as before.
+// COL_VAL has a kernel of its own, k_spmv_val below.
 enum { COL_J = 0, COL_ID = 1, COL_ROW = 2, COL_VAL = 3 };
-#ifndef LSSP_AMD_SPMV_VB
-#define LSSP_AMD_SPMV_VB 4
-#endif
-#ifndef LSSP_AMD_SPMV_UNI
-#define LSSP_AMD_SPMV_UNI 1
-#endif
-#ifndef LSSP_AMD_SPMV_WAVES
+#ifndef LSSP_AMD_SPMV_WAVES  // (the waves per SIMD both kernels are compiled for: see k_spmv_val)
 #define LSSP_AMD_SPMV_WAVES 5
 #endif
-constexpr int SPMV_VB = LSSP_AMD_SPMV_VB;
-constexpr bool SPMV_UNI = LSSP_AMD_SPMV_UNI != 0;
-// a uniform wave's row of L entries: the products added in CSR order onto +0.0,
-// the values read per lane from the LDS table (sv[u][c])
-template <int L>
-__device__ __forceinline__ double uni_row(const double (&xv)[8], const double (*sv)[ROWVAL_MAX], unsigned c)
+
+// What the three product kernels (k_spmv3, k_spmv_val, k_spmv_sell) share is
+// stated once here.  Operand order inside every expression is the reference's
+// (mvops.cxx) and, with -ffp-contract=off, decides the result's bits.
+//
+// The workgroup's block: stream blockIdx.x % K holds `per` consecutive blocks,
+// of which this workgroup takes number pos
+__device__ __forceinline__ long spmv_stream_block(const SpmvArgs &a, long per, long pos)
 {
-    double s = 0;
-#pragma unroll
-    for (int u = 0; u < L; u++) s += xv[u] * sv[u][c];
-    return s;
+    return (blockIdx.x % a.streams) * per + pos;
 }
+// ... and that block's place in the column-group order (spmv_group_env), when one is set
+__device__ __forceinline__ long spmv_group_block(const SpmvArgs &a, long lb)
+{
+    if (a.pbpp > 0 && lb < (long)a.pbpp * a.pz) {  // (32-bit: the grouped blocks are fewer than 2^31)
+        const unsigned ub = (unsigned)lb, gs = (unsigned)(a.pw * a.pz), g = ub / gs, rem = ub - g * gs;
+        lb = (long)((rem / a.pw) * a.pbpp + g * a.pw + rem % a.pw);
+    }
+    return lb;
+}
+// The fused dots' second operands of row rr, loaded up front with the row's
+// other inputs (the compiler may not move them above the z store: w0 / w1 may
+// alias z, and then they are read as the value just stored, zv, in
+// spmv_dot_terms).  ntv: as non-temporal loads (SpmvArgs::ntv); w0_staged: the
+// kernel has w0's element elsewhere (k_spmv_sell: w0 == x, in its LDS ring)
+template <int NRED>
+__device__ __forceinline__ void spmv_dot_loads(const SpmvArgs &a, int rr, bool ntv, bool w0_staged, double &w0p,
+                                               double &w1p)
+{
+    w0p = 0.0;
+    w1p = 0.0;
+    if (NRED > 0) {
+        if (ntv) {
+            if (a.w0 != a.z && !w0_staged) w0p = __builtin_nontemporal_load(a.w0 + rr);
+            if (NRED > 1 && a.w1 && a.w1 != a.z) w1p = __builtin_nontemporal_load(a.w1 + rr);
+        } else {
+            if (a.w0 != a.z && !w0_staged) w0p = a.w0[rr];
+            if (NRED > 1 && a.w1 && a.w1 != a.z) w1p = a.w1[rr];
+        }
+    }
+}
+// The output rule: row r's element of z from the row's sum
+template <int EPI>
+__device__ __forceinline__ double spmv_out(const SpmvArgs &a, int r, double sum)
+{
+    double zv;
+    if (EPI == EPI_MXY) zv = sum;
+    else if (EPI == EPI_AMXY) zv = sum * a.alpha;
+    else if (EPI == EPI_AXPBY) zv = a.y[r] * a.beta + a.alpha * sum;
+    else zv = a.alpha * sum;
+    return zv;
+}
+// The dot-term rule: v[0] = z w0, v[1] = z (w1 ? w1 : z), v[2] = w0 w0 for a
+// row of the matrix (in), +0.0 for a lane past it.  An operand that is z itself
+// is the value just stored, zv, and not a load
+template <int NRED>
+__device__ __forceinline__ void spmv_dot_terms(const SpmvArgs &a, bool in, double zv, double w0p, double w1p,
+                                               double (&v)[NRED > 0 ? NRED : 1])
+{
+    if (in) {
+        v[0] = zv * (a.w0 == a.z ? zv : w0p);
+        if (NRED > 1) v[NRED > 1 ? 1 : 0] = zv * (a.w1 && a.w1 != a.z ? w1p : zv);
+        if (NRED > 2) v[NRED > 2 ? 2 : 0] = w0p * w0p;  // (launch_spmv: w0 != z)
+    } else {
+#pragma unroll
+        for (int q = 0; q < NRED; q++) v[q] = 0.0;
+    }
+}
+
 template <int EPI, int NRED, int CM>
 __global__ __launch_bounds__(256)
 #if LSSP_AMD_SPMV_WAVES > 0
@@ -454,162 +479,24 @@ __attribute__((amdgpu_waves_per_eu(LSSP_AMD_SPMV_WAVES)))
 #endif
 void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
 {
-    constexpr bool CMP = CM == COL_ID, ROW = CM == COL_ROW, VAL = CM == COL_VAL;
+    static_assert(CM != COL_VAL, "k_spmv_val");
+    constexpr bool CMP = CM == COL_ID, ROW = CM == COL_ROW;
     static_assert(256 * 8 <= SPMV_CAP, "a row-coded block fits the staging buffer");
     constexpr int NX2 = (SPMV_CAP / 2 + 1 + 255) / 256;  // double2 loads per lane
     constexpr int NJ4 = CMP ? 1 : (SPMV_CAP / 4 + 1 + 255) / 256;  // int4 loads per lane (16 ids when CMP)
-    __shared__ __attribute__((aligned(16))) double sx[VAL ? 2 : SPMV_CAP + 2];
-    __shared__ __attribute__((aligned(16))) int sj[ROW || VAL ? 1 : CMP ? SPMV_CAP / 4 + 8 : SPMV_CAP + 4];
+    __shared__ __attribute__((aligned(16))) double sx[SPMV_CAP + 2];
+    __shared__ __attribute__((aligned(16))) int sj[ROW ? 1 : CMP ? SPMV_CAP / 4 + 8 : SPMV_CAP + 4];
     __shared__ int soff[CMP || ROW ? 256 : 1];
     __shared__ unsigned long long spat[ROW ? 256 : 1];
-    __shared__ double sval[VAL ? ROWPAT_LEN : 1][VAL ? ROWVAL_MAX : 1];
-    __shared__ int svoff[VAL ? ROWPAT_LEN + 1 : 1][VAL ? ROWVAL_MAX : 1];
     __shared__ int swt[ROW ? 4 : 1];  // the waves' entry counts
     __shared__ double lds[MAX_SLOTS][4];
     // the guard is read with the row bounds and tested before the entries are
     // loaded: its round trip overlaps theirs instead of preceding it
     const double gv = a.guard ? *a.guard : 0.0;
-    if constexpr (VAL) {
-        const int tid = threadIdx.x;
-        const long per = (nblk + a.streams - 1) / a.streams;  // blocks per stream
-        const long pos0 = (long)(blockIdx.x / a.streams) * SPMV_VB;
-        const long lb0 = (blockIdx.x % a.streams) * per + pos0;
-        if (pos0 >= per || lb0 >= nblk) return;
-        long blk[SPMV_VB];
-        bool live[SPMV_VB];
-        unsigned code[SPMV_VB];
-        double w0p[SPMV_VB], w1p[SPMV_VB], sum[SPMV_VB];
-#pragma unroll
-        for (int j = 0; j < SPMV_VB; j++) {
-            long lb = lb0 + j;
-            live[j] = pos0 + j < per && lb < nblk;  // the same for every lane
-            if (!live[j]) lb = lb0;
-            if (a.pbpp > 0 && lb < (long)a.pbpp * a.pz) {  // (32-bit: the grouped blocks are fewer than 2^31)
-                const unsigned ub = (unsigned)lb, gs = (unsigned)(a.pw * a.pz), g = ub / gs, rem = ub - g * gs;
-                lb = (long)((rem / a.pw) * a.pbpp + g * a.pw + rem % a.pw);
-            }
-            blk[j] = a.blk0 + lb;
-            const int rr = min((int)(blk[j] * 256) + tid, a.nrows - 1);
-            code[j] = __builtin_nontemporal_load(a.Av + rr);
-            w0p[j] = w1p[j] = 0.0;
-            if (NRED > 0) {  // as below
-                if (a.ntv) {
-                    if (a.w0 != a.z) w0p[j] = __builtin_nontemporal_load(a.w0 + rr);
-                    if (NRED > 1 && a.w1 && a.w1 != a.z) w1p[j] = __builtin_nontemporal_load(a.w1 + rr);
-                } else {
-                    if (a.w0 != a.z) w0p[j] = a.w0[rr];
-                    if (NRED > 1 && a.w1 && a.w1 != a.z) w1p[j] = a.w1[rr];
-                }
-            }
-        }
-        // the table's values (rows 1 .. 8 of d_val) and the decoded patterns: entry c's
-        // column offsets in rows 0 .. 7 of d_voff, its length in row 8
-        for (int t = tid; t < (ROWPAT_LEN + 1) * a.nval; t += 256) {
-            const int q = t / a.nval, c = t - q * a.nval;
-            svoff[q][c] = a.voff[t];
-            if (q < ROWPAT_LEN) sval[q][c] = __longlong_as_double((long long)a.val[a.nval + t]);
-        }
-        if (gv != 0.0) return;
-        int len[SPMV_VB];
-        double xv[SPMV_VB][8];
-        // which of the wave's blocks are uniform: 64 equal codes, all rows in the matrix
-        bool uni[SPMV_VB];
-        int ulen[SPMV_VB];  // (kept apart from len: a scalar)
-        const int wrow = __builtin_amdgcn_readfirstlane(tid & ~63);
-#pragma unroll
-        for (int j = 0; j < SPMV_VB; j++) {
-            uni[j] = false;
-            ulen[j] = 0;
-            if (SPMV_UNI && NRED > 0 && a.uni) {  // (the plain product measured slower with it: DESIGN 6.0b)
-                const unsigned c0 = __builtin_amdgcn_readfirstlane(code[j]);
-                const int rw = (int)(blk[j] * 256) + wrow;  // the wave's first row
-                uni[j] = live[j] && rw + 63 < a.nrows && __ballot(code[j] != c0) == 0;
-            }
-        }
-        __syncthreads();
-        // every x gather of every block is issued before the first product, with no
-        // branch on the row's length around them: the table repeats a row's last
-        // offset past its length (an empty row's are 0 and read x[0]), a lane past
-        // the matrix's last row gathers for that row, and entry 7 is skipped
-        // unless some row of the matrix has 8 entries
-#pragma unroll
-        for (int j = 0; j < SPMV_VB; j++) {
-            const int r = (int)(blk[j] * 256) + tid;
-            const int lt = svoff[ROWPAT_LEN][code[j]];
-            const double *xb = a.x + (lt > 0 ? min(r, a.nrows - 1) : 0);
-            len[j] = r < a.nrows && live[j] ? lt : 0;
-            if (uni[j]) ulen[j] = __builtin_amdgcn_readfirstlane(lt);
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (u == 7 && !a.v8) continue;
-                xv[j][u] = xb[svoff[u][code[j]]];
-            }
-        }
-        // the products, added in CSR order.  An entry past the row's length adds
-        // +0.0 instead of its product, which leaves the sum's bits as they are: a
-        // sum that starts at +0.0 is never -0.0 (no branch per entry)
-#pragma unroll
-        for (int j = 0; j < SPMV_VB; j++) {
-            sum[j] = 0;
-            if (uni[j]) {
-                // the length resolved once per block: entries past it are not added, which
-                // is adding +0.0 (a wave of empty rows: no product, +0.0)
-                switch (ulen[j]) {
-                case 1: sum[j] = uni_row<1>(xv[j], sval, code[j]); break;
-                case 2: sum[j] = uni_row<2>(xv[j], sval, code[j]); break;
-                case 3: sum[j] = uni_row<3>(xv[j], sval, code[j]); break;
-                case 4: sum[j] = uni_row<4>(xv[j], sval, code[j]); break;
-                case 5: sum[j] = uni_row<5>(xv[j], sval, code[j]); break;
-                case 6: sum[j] = uni_row<6>(xv[j], sval, code[j]); break;
-                case 7: sum[j] = uni_row<7>(xv[j], sval, code[j]); break;
-                case 8: sum[j] = uni_row<8>(xv[j], sval, code[j]); break;  // (some row has 8 entries: a.v8)
-                default: break;
-                }
-                continue;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (u == 7 && !a.v8) continue;
-                const double pr = xv[j][u] * sval[u][code[j]];
-                sum[j] += u < len[j] ? pr : 0.0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < SPMV_VB; j++) {
-            if (!live[j]) continue;
-            const int r = (int)(blk[j] * 256) + tid;
-            double zv = 0;
-            if (r < a.nrows) {
-                if (EPI == EPI_MXY) zv = sum[j];
-                else if (EPI == EPI_AMXY) zv = sum[j] * a.alpha;
-                else if (EPI == EPI_AXPBY) zv = a.y[r] * a.beta + a.alpha * sum[j];
-                else zv = a.alpha * sum[j];
-                if (a.ntv) __builtin_nontemporal_store(zv, a.z + r);
-                else a.z[r] = zv;
-            }
-            if (NRED > 0) {
-                double v[NRED > 0 ? NRED : 1];
-                if (r < a.nrows) {
-                    v[0] = zv * (a.w0 == a.z ? zv : w0p[j]);
-                    if (NRED > 1) v[NRED > 1 ? 1 : 0] = zv * (a.w1 && a.w1 != a.z ? w1p[j] : zv);
-                    if (NRED > 2) v[NRED > 2 ? 2 : 0] = w0p[j] * w0p[j];  // (launch_spmv: w0 != z)
-                } else {
-#pragma unroll
-                    for (int q = 0; q < NRED; q++) v[q] = 0.0;
-                }
-                chunk_reduce<NRED>(v, a.part, a.pcap, blk[j], lds);
-            }
-        }
-        return;
-    }
     const long per = gridDim.x / a.streams;
-    long lb = (blockIdx.x % a.streams) * per + blockIdx.x / a.streams;
+    const long lb = spmv_stream_block(a, per, blockIdx.x / a.streams);
     if (lb >= nblk) return;
-    if (a.pbpp > 0 && lb < (long)a.pbpp * a.pz) {
-        const long gs = (long)a.pw * a.pz, g = lb / gs, rem = lb - g * gs;
-        lb = (rem / a.pw) * a.pbpp + g * a.pw + rem % a.pw;
-    }
-    const long blk = a.blk0 + lb;
+    const long blk = a.blk0 + spmv_group_block(a, lb);
     const int r0 = (int)(blk * 256);
     const int tid = threadIdx.x;
     const int r = r0 + tid;
@@ -621,19 +508,8 @@ void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
     unsigned code = 0;
     if (ROW) code = a.Ac[rr];
     else rb = a.Ap[rr], re = a.Ap[rr + 1];
-    // the fused dots' second operands, loaded up front with the row bounds (the
-    // compiler may not move them above the z store: w0 / w1 may alias z, and
-    // then they are read as the value just stored, zv, below)
-    double w0p = 0.0, w1p = 0.0;
-    if (NRED > 0) {
-        if (a.ntv) {
-            if (a.w0 != a.z) w0p = __builtin_nontemporal_load(a.w0 + rr);
-            if (NRED > 1 && a.w1 && a.w1 != a.z) w1p = __builtin_nontemporal_load(a.w1 + rr);
-        } else {
-            if (a.w0 != a.z) w0p = a.w0[rr];
-            if (NRED > 1 && a.w1 && a.w1 != a.z) w1p = a.w1[rr];
-        }
-    }
+    double w0p, w1p;
+    spmv_dot_loads<NRED>(a, rr, a.ntv, false, w0p, w1p);
     if (gv != 0.0) return;  // a batched iteration past the stop (lssp_amd_ctx::guard)
     double sum = 0;
     if (ROW || cnt <= SPMV_CAP) {
@@ -731,24 +607,181 @@ void k_spmv3(SpmvArgs a, long nblk, long nnz_pad)
     }
     double zv = 0;
     if (r < a.nrows) {
-        if (EPI == EPI_MXY) zv = sum;
-        else if (EPI == EPI_AMXY) zv = sum * a.alpha;
-        else if (EPI == EPI_AXPBY) zv = a.y[r] * a.beta + a.alpha * sum;
-        else zv = a.alpha * sum;
+        zv = spmv_out<EPI>(a, r, sum);
         if (a.ntv) __builtin_nontemporal_store(zv, a.z + r);
         else a.z[r] = zv;
     }
     if (NRED > 0) {
         double v[NRED > 0 ? NRED : 1];
-        if (r < a.nrows) {
-            v[0] = zv * (a.w0 == a.z ? zv : w0p);
-            if (NRED > 1) v[NRED > 1 ? 1 : 0] = zv * (a.w1 && a.w1 != a.z ? w1p : zv);
-            if (NRED > 2) v[NRED > 2 ? 2 : 0] = w0p * w0p;  // (launch_spmv: w0 != z)
-        } else {
-#pragma unroll
-            for (int q = 0; q < NRED; q++) v[q] = 0.0;
-        }
+        spmv_dot_terms<NRED>(a, r < a.nrows, zv, w0p, w1p, v);
         chunk_reduce<NRED>(v, a.part, a.pcap, blk, lds);
+    }
+}
+
+// COL_VAL takes the values too from the row's code (lssp_amd_mat::Av: a table
+// of the matrix's distinct rows, pattern key and 8 values each, of which the
+// workgroup copies the nval live entries to LDS): 1 byte per row and neither
+// Ap nor Ax, so no staging, no scan, and one barrier, behind the table copy.
+// With the value stream gone the kernel is paced by the instructions it issues
+// per entry, so the table is read in its decoded form (lssp_amd_mat::d_voff:
+// a column offset per entry and the row's length) and not through thr / off.
+// A workgroup walks SPMV_VB consecutive blocks of its stream with that one
+// copy: the codes and dot operands of all of them are loaded up front, then
+// all their x gathers are issued, then each block runs its own epilogue and
+// writes its own rows and chunk partial, as a workgroup of its own would.
+// Uniform waves (LSSP_AMD_SPMV_UNI): on a structured grid most waves hold 64
+// rows with one code (216^3: 2/3 of them), so the row's length is the same in
+// every lane.  A wave whose 64 code bytes of a live block are equal and whose
+// rows all lie below nrows takes the length as a scalar (readfirstlane of the
+// LDS word) and resolves it once per block, by a uniform switch: its products
+// are a straight multiply-add chain of exactly that length, with no compare and
+// select per entry (7-entry rows: 14 vector instructions for 36).  Offsets and
+// values it still reads per lane from the LDS table: taking them as scalars too
+// (scalar loads from the global table, gathers from a scalar base) issued a
+// third of the instructions and measured slower -- DESIGN 6.0b.  Same entries,
+// same order, each product rounded on its own: the bits of the per-lane path,
+// which every other wave of the workgroup still takes.
+// LSSP_AMD_SPMV_WAVES: the waves per SIMD the register allocation aims at.  5
+// holds every k_spmv_val instance to 96 VGPRs (the three-dot one had 106 and
+// ran 4 waves).  The attribute is a lower bound only: it caps the registers at
+// what five waves allow and raises nothing, so k_spmv3's instances, which
+// carry it too (under 48 VGPRs: 6 to 8 waves), compile as they would without.
+#ifndef LSSP_AMD_SPMV_VB
+#define LSSP_AMD_SPMV_VB 4
+#endif
+#ifndef LSSP_AMD_SPMV_UNI
+#define LSSP_AMD_SPMV_UNI 1
+#endif
+constexpr int SPMV_VB = LSSP_AMD_SPMV_VB;
+constexpr bool SPMV_UNI = LSSP_AMD_SPMV_UNI != 0;
+// a uniform wave's row of L entries: the products added in CSR order onto +0.0,
+// the values read per lane from the LDS table (sv[u][c])
+template <int L>
+__device__ __forceinline__ double uni_row(const double (&xv)[8], const double (*sv)[ROWVAL_MAX], unsigned c)
+{
+    double s = 0;
+#pragma unroll
+    for (int u = 0; u < L; u++) s += xv[u] * sv[u][c];
+    return s;
+}
+template <int EPI, int NRED>
+__global__ __launch_bounds__(256)
+#if LSSP_AMD_SPMV_WAVES > 0
+__attribute__((amdgpu_waves_per_eu(LSSP_AMD_SPMV_WAVES)))
+#endif
+void k_spmv_val(SpmvArgs a, long nblk)
+{
+    __shared__ double sval[ROWPAT_LEN][ROWVAL_MAX];
+    __shared__ int svoff[ROWPAT_LEN + 1][ROWVAL_MAX];
+    __shared__ double lds[MAX_SLOTS][4];
+    // the guard: as in k_spmv3
+    const double gv = a.guard ? *a.guard : 0.0;
+    const int tid = threadIdx.x;
+    const long per = (nblk + a.streams - 1) / a.streams;  // blocks per stream
+    const long pos0 = (long)(blockIdx.x / a.streams) * SPMV_VB;
+    const long lb0 = spmv_stream_block(a, per, pos0);
+    if (pos0 >= per || lb0 >= nblk) return;
+    long blk[SPMV_VB];
+    bool live[SPMV_VB];
+    unsigned code[SPMV_VB];
+    double w0p[SPMV_VB], w1p[SPMV_VB], sum[SPMV_VB];
+#pragma unroll
+    for (int j = 0; j < SPMV_VB; j++) {
+        long lb = lb0 + j;
+        live[j] = pos0 + j < per && lb < nblk;  // the same for every lane
+        if (!live[j]) lb = lb0;
+        blk[j] = a.blk0 + spmv_group_block(a, lb);
+        const int rr = min((int)(blk[j] * 256) + tid, a.nrows - 1);
+        code[j] = __builtin_nontemporal_load(a.Av + rr);
+        spmv_dot_loads<NRED>(a, rr, a.ntv, false, w0p[j], w1p[j]);
+    }
+    // the table's values (rows 1 .. 8 of d_val) and the decoded patterns: entry c's
+    // column offsets in rows 0 .. 7 of d_voff, its length in row 8
+    for (int t = tid; t < (ROWPAT_LEN + 1) * a.nval; t += 256) {
+        const int q = t / a.nval, c = t - q * a.nval;
+        svoff[q][c] = a.voff[t];
+        if (q < ROWPAT_LEN) sval[q][c] = __longlong_as_double((long long)a.val[a.nval + t]);
+    }
+    if (gv != 0.0) return;
+    int len[SPMV_VB];
+    double xv[SPMV_VB][8];
+    // which of the wave's blocks are uniform: 64 equal codes, all rows in the matrix
+    bool uni[SPMV_VB];
+    int ulen[SPMV_VB];  // (kept apart from len: a scalar)
+    const int wrow = __builtin_amdgcn_readfirstlane(tid & ~63);
+#pragma unroll
+    for (int j = 0; j < SPMV_VB; j++) {
+        uni[j] = false;
+        ulen[j] = 0;
+        if (SPMV_UNI && NRED > 0 && a.uni) {  // (the plain product measured slower with it: DESIGN 6.0b)
+            const unsigned c0 = __builtin_amdgcn_readfirstlane(code[j]);
+            const int rw = (int)(blk[j] * 256) + wrow;  // the wave's first row
+            uni[j] = live[j] && rw + 63 < a.nrows && __ballot(code[j] != c0) == 0;
+        }
+    }
+    __syncthreads();
+    // every x gather of every block is issued before the first product, with no
+    // branch on the row's length around them: the table repeats a row's last
+    // offset past its length (an empty row's are 0 and read x[0]), a lane past
+    // the matrix's last row gathers for that row, and entry 7 is skipped
+    // unless some row of the matrix has 8 entries
+#pragma unroll
+    for (int j = 0; j < SPMV_VB; j++) {
+        const int r = (int)(blk[j] * 256) + tid;
+        const int lt = svoff[ROWPAT_LEN][code[j]];
+        const double *xb = a.x + (lt > 0 ? min(r, a.nrows - 1) : 0);
+        len[j] = r < a.nrows && live[j] ? lt : 0;
+        if (uni[j]) ulen[j] = __builtin_amdgcn_readfirstlane(lt);
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (u == 7 && !a.v8) continue;
+            xv[j][u] = xb[svoff[u][code[j]]];
+        }
+    }
+    // the products, added in CSR order.  An entry past the row's length adds
+    // +0.0 instead of its product, which leaves the sum's bits as they are: a
+    // sum that starts at +0.0 is never -0.0 (no branch per entry)
+#pragma unroll
+    for (int j = 0; j < SPMV_VB; j++) {
+        sum[j] = 0;
+        if (uni[j]) {
+            // the length resolved once per block: entries past it are not added, which
+            // is adding +0.0 (a wave of empty rows: no product, +0.0)
+            switch (ulen[j]) {
+            case 1: sum[j] = uni_row<1>(xv[j], sval, code[j]); break;
+            case 2: sum[j] = uni_row<2>(xv[j], sval, code[j]); break;
+            case 3: sum[j] = uni_row<3>(xv[j], sval, code[j]); break;
+            case 4: sum[j] = uni_row<4>(xv[j], sval, code[j]); break;
+            case 5: sum[j] = uni_row<5>(xv[j], sval, code[j]); break;
+            case 6: sum[j] = uni_row<6>(xv[j], sval, code[j]); break;
+            case 7: sum[j] = uni_row<7>(xv[j], sval, code[j]); break;
+            case 8: sum[j] = uni_row<8>(xv[j], sval, code[j]); break;  // (some row has 8 entries: a.v8)
+            default: break;
+            }
+            continue;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (u == 7 && !a.v8) continue;
+            const double pr = xv[j][u] * sval[u][code[j]];
+            sum[j] += u < len[j] ? pr : 0.0;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < SPMV_VB; j++) {
+        if (!live[j]) continue;
+        const int r = (int)(blk[j] * 256) + tid;
+        double zv = 0;
+        if (r < a.nrows) {
+            zv = spmv_out<EPI>(a, r, sum[j]);
+            if (a.ntv) __builtin_nontemporal_store(zv, a.z + r);
+            else a.z[r] = zv;
+        }
+        if (NRED > 0) {
+            double v[NRED > 0 ? NRED : 1];
+            spmv_dot_terms<NRED>(a, r < a.nrows, zv, w0p[j], w1p[j], v);
+            chunk_reduce<NRED>(v, a.part, a.pcap, blk[j], lds);
+        }
     }
 }
 
@@ -832,12 +865,7 @@ __global__ __launch_bounds__(WIN_ROWS) void k_spmv_sell(SpmvArgs a, const int *_
         const int r = (int)(b * WIN_ROWS) + tid, rr = min(r, a.nrows - 1);
         const int r0 = (int)(b * WIN_ROWS), r1 = min(r0 + WIN_ROWS, a.nrows);
         const bool w0x = NRED > 0 && a.w0 == a.x && a.w0 != a.z && r0 >= mlo && r1 <= mhi;
-        q.w0p = 0.0;
-        q.w1p = 0.0;
-        if (NRED > 0) {
-            if (a.w0 != a.z && !w0x) q.w0p = a.w0[rr];
-            if (NRED > 1 && a.w1 && a.w1 != a.z) q.w1p = a.w1[rr];
-        }
+        spmv_dot_loads<NRED>(a, rr, false, w0x, q.w0p, q.w1p);
     };
     auto meta = [&](long b, int &mlo, int &mhi, int &sb) {
         mlo = win[2 * b] & ~1;
@@ -894,21 +922,12 @@ __global__ __launch_bounds__(WIN_ROWS) void k_spmv_sell(SpmvArgs a, const int *_
         if (w0x && r < a.nrows) w0p = sxw[r & MASK];
         double zv = 0;
         if (r < a.nrows) {
-            if (EPI == EPI_MXY) zv = sum;
-            else if (EPI == EPI_AMXY) zv = sum * a.alpha;
-            else if (EPI == EPI_AXPBY) zv = a.y[r] * a.beta + a.alpha * sum;
-            else zv = a.alpha * sum;
+            zv = spmv_out<EPI>(a, r, sum);
             a.z[r] = zv;
         }
         if (NRED > 0) {
             double v[NRED > 0 ? NRED : 1];
-            if (r < a.nrows) {
-                v[0] = zv * (a.w0 == a.z ? zv : w0p);
-                if (NRED > 1) v[NRED > 1 ? 1 : 0] = zv * (a.w1 && a.w1 != a.z ? cur.w1p : zv);
-            } else {
-#pragma unroll
-                for (int q = 0; q < NRED; q++) v[q] = 0.0;
-            }
+            spmv_dot_terms<NRED>(a, r < a.nrows, zv, w0p, cur.w1p, v);
             // chunk_reduce's order for each of the 4 chunks (waves 4q .. 4q+3);
             // the next block writes lds only after three more barriers
             const int q = wave >> 2;
@@ -965,72 +984,33 @@ static void spmv_sell_dispatch(const SpmvArgs &a, const lssp_amd_mat *A, int nre
 // (profiles/r05/r05l_spmv_group_order.txt).  Automatic for planes of >= 512
 // blocks (128 Ki rows; smaller planes keep x in L2 anyway) with W = 128;
 // LSSP_AMD_SPMV_ORDER=W forces a width (0: natural order; tests, A/B runs).
-static int spmv_group_env()
+//
+// The LSSP_AMD_SPMV_* knobs (tests, A/B runs), all read once, at the first
+// use of any: the environment's integer, or the value of a knob left unset
+enum { KNOB_ORDER, KNOB_NTV, KNOB_STREAMS, KNOB_ROWCODE, KNOB_VALCODE, KNOB_UNIFORM, KNOB_COUNT };
+static int spmv_knob(int which)
 {
-    static const int k = [] {
-        const char *e = getenv("LSSP_AMD_SPMV_ORDER");
-        return e ? std::max(0, atoi(e)) : -1;
+    static const std::array<int, KNOB_COUNT> val = [] {
+        const struct {
+            const char *name;
+            int unset;
+        } knob[KNOB_COUNT] = {{"LSSP_AMD_SPMV_ORDER", -1},  {"LSSP_AMD_SPMV_NTV", 1},     {"LSSP_AMD_SPMV_STREAMS", 0},
+                              {"LSSP_AMD_SPMV_ROWCODE", 1}, {"LSSP_AMD_SPMV_VALCODE", 1}, {"LSSP_AMD_SPMV_UNIFORM", 1}};
+        std::array<int, KNOB_COUNT> v;
+        for (int k = 0; k < KNOB_COUNT; k++) {
+            const char *e = getenv(knob[k].name);
+            v[k] = e ? atoi(e) : knob[k].unset;
+            if (e && k == KNOB_ORDER) v[k] = std::max(0, v[k]);  // a width, or 0
+            if (k == KNOB_STREAMS && !(v[k] >= 8 && v[k] % 8 == 0 && v[k] <= 4096)) v[k] = 0;  // a multiple of 8
+        }
+        return v;
     }();
-    return k;
-}
-
-// w0 / w1 loads and the z store as non-temporal accesses (no other block
-// re-reads them): the 8-rank slab's iteration -0.3 .. -0.6 %.
-// LSSP_AMD_SPMV_NTV=0 turns them off (A/B runs).
-static int spmv_ntv()
-{
-    static const int k = [] {
-        const char *e = getenv("LSSP_AMD_SPMV_NTV");
-        return e ? atoi(e) : 1;
-    }();
-    return k;
-}
-
-// LSSP_AMD_SPMV_STREAMS=K forces K streams (A/B runs); 0: the matrix's own
-// choice (tune_spmv_streams), 8 when it has none
-static int spmv_streams_env()
-{
-    static const int k = [] {
-        const char *e = getenv("LSSP_AMD_SPMV_STREAMS");
-        const int v = e ? atoi(e) : 0;
-        return v >= 8 && v % 8 == 0 && v <= 4096 ? v : 0;
-    }();
-    return k;
-}
-// LSSP_AMD_SPMV_ROWCODE=0: a row-coded matrix's product reads the ids
-// (COL_ID) all the same (tests, A/B runs)
-static int spmv_rowcode()
-{
-    static const int k = [] {
-        const char *e = getenv("LSSP_AMD_SPMV_ROWCODE");
-        return e ? atoi(e) : 1;
-    }();
-    return k;
-}
-// LSSP_AMD_SPMV_VALCODE=0: a value-coded matrix's product reads Ax (COL_ROW)
-// all the same (tests, A/B runs); LSSP_AMD_SPMV_ROWCODE=0 implies it
-static int spmv_valcode()
-{
-    static const int k = [] {
-        const char *e = getenv("LSSP_AMD_SPMV_VALCODE");
-        return e ? atoi(e) : 1;
-    }();
-    return k;
-}
-// LSSP_AMD_SPMV_UNIFORM=0: every wave of a value-coded product takes the
-// per-lane path (tests, A/B runs); the same kernel, so tune_spmv_streams times
-// what runs
-static int spmv_uniform()
-{
-    static const int k = [] {
-        const char *e = getenv("LSSP_AMD_SPMV_UNIFORM");
-        return e ? atoi(e) : 1;
-    }();
-    return k;
+    return val[which];
 }
 static int spmv_streams(const lssp_amd_mat *A)
 {
-    const int e = spmv_streams_env();
+    // LSSP_AMD_SPMV_STREAMS=K forces K streams; 0: the matrix's own choice (tune_spmv_streams), 8 when it has none
+    const int e = spmv_knob(KNOB_STREAMS);
     return e ? e : A->streams > 0 ? A->streams : 8;
 }
 
@@ -1040,10 +1020,17 @@ static void spmv_dispatch(const SpmvArgs &a, int nred, long nblocks, hipStream_t
     long per = (nblocks + a.streams - 1) / a.streams;                    // blocks per stream
     if (CM == COL_VAL) per = (per + SPMV_VB - 1) / SPMV_VB;               // workgroups per stream
     const long g = per * a.streams;                                      // a multiple of K: whole stream shares
-    if (nred == 0) k_spmv3<EPI, 0, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
-    else if (nred == 1) k_spmv3<EPI, 1, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
-    else if (nred == 2 || EPI != EPI_AMX) k_spmv3<EPI, 2, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
-    else k_spmv3<EPI_AMX, 3, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+    if constexpr (CM == COL_VAL) {
+        if (nred == 0) k_spmv_val<EPI, 0><<<g, 256, 0, s>>>(a, nblocks);
+        else if (nred == 1) k_spmv_val<EPI, 1><<<g, 256, 0, s>>>(a, nblocks);
+        else if (nred == 2 || EPI != EPI_AMX) k_spmv_val<EPI, 2><<<g, 256, 0, s>>>(a, nblocks);
+        else k_spmv_val<EPI_AMX, 3><<<g, 256, 0, s>>>(a, nblocks);
+    } else {
+        if (nred == 0) k_spmv3<EPI, 0, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+        else if (nred == 1) k_spmv3<EPI, 1, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+        else if (nred == 2 || EPI != EPI_AMX) k_spmv3<EPI, 2, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+        else k_spmv3<EPI_AMX, 3, CM><<<g, 256, 0, s>>>(a, nblocks, nnz_pad);
+    }
 }
 
 template <int EPI>
@@ -1069,27 +1056,32 @@ int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, c
     if (nred == 3 && (epi != EPI_AMX || !w0 || w0 == z || w1)) return LSSP_AMD_EINVAL;
     const long nb = ce - cb;
     if (nb == 0) return LSSP_AMD_OK;
+    // LSSP_AMD_SPMV_NTV=0: w0 / w1 loads and the z store as ordinary accesses (non-temporal, as no other block
+    // re-reads them: the 8-rank slab's iteration -0.3 .. -0.6 %)
     SpmvArgs a{A->nrows, A->Ap, A->Aj, A->Ax, x, y, z, alpha, beta, w0, w1, c->d_part, c->part_cap,
-               A->Ad, A->d_off, A->ndiag, c->guard, cb, spmv_streams(A), 0, 0, 0, spmv_ntv(),
+               A->Ad, A->d_off, A->ndiag, c->guard, cb, spmv_streams(A), 0, 0, 0, spmv_knob(KNOB_NTV),
                nullptr, nullptr, 0, {0, 0, 0, 0, 0, 0, 0, 0}, nullptr, nullptr, nullptr, 0, 0, 0};
-    if (A->npat > 0 && spmv_rowcode()) {
+    // LSSP_AMD_SPMV_ROWCODE=0: a row-coded matrix's product reads the ids (COL_ID) all the same
+    if (A->npat > 0 && spmv_knob(KNOB_ROWCODE)) {
         a.Ac = A->Ac;
         a.pat = A->d_pat;
         a.npat = A->npat;
         memcpy(a.thr, A->pat_thr, sizeof(a.thr));
-        if (A->nval > 0 && spmv_valcode()) {
+        // LSSP_AMD_SPMV_VALCODE=0: a value-coded matrix's product reads Ax (COL_ROW) all the same; ROWCODE=0 implies it
+        if (A->nval > 0 && spmv_knob(KNOB_VALCODE)) {
             a.Av = A->Av;
             a.val = A->d_val;
             a.voff = A->d_voff;
             a.nval = A->nval;
             a.v8 = A->val_thr[7] < A->nval;
-            a.uni = spmv_uniform() != 0;
+            // LSSP_AMD_SPMV_UNIFORM=0: every wave takes the per-lane path; the same kernel, so tune_spmv_streams times what runs
+            a.uni = spmv_knob(KNOB_UNIFORM) != 0;
         }
     }
     const long plane = A->max_off_int;
     if (A->ndiag > 0 && plane >= 256 * 8 && plane % 256 == 0) {
         const long bpp = plane / 256;
-        const int env = spmv_group_env();
+        const int env = spmv_knob(KNOB_ORDER);  // LSSP_AMD_SPMV_ORDER=W forces a group width (0: natural order)
         const int pw = env >= 0 ? env : (bpp >= 512 && bpp % 128 == 0 ? 128 : 0);
         if (pw > 0 && bpp % pw == 0 && nb / bpp >= 2) {
             a.pbpp = (int)bpp;
@@ -1129,7 +1121,7 @@ int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, c
 int tune_spmv_streams(lssp_amd_ctx *c, lssp_amd_mat *A)
 {
     A->streams = 0;
-    if (spmv_streams_env() || A->nrows < (1 << 22) || A->d_win || A->nhalo > 0 || A->n_global != A->nrows)
+    if (spmv_knob(KNOB_STREAMS) || A->nrows < (1 << 22) || A->d_win || A->nhalo > 0 || A->n_global != A->nrows)
         return LSSP_AMD_OK;
     double *x = nullptr, *z = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;

@@ -9,7 +9,8 @@ lssp_amd_mat_from_device) -- bitwise:
     sides of the sort's one-thread limit (64 entries),
   * the device column sort against the host one (lssp_amd.sort_columns),
   * a handle from device arrays against lssp_amd_mat_upload of the same arrays:
-    layout, bytes, all four products, a solve,
+    layout, bytes, all four products (both handles come from one builder, so
+    each is held to the oracle's products as well), a solve,
   * COO in HBM -> CSR -> sorted -> handle -> solve with no host copy of the matrix,
   * malformed inputs return LSSP_AMD_EINVAL instead of faulting.
 """
@@ -190,6 +191,16 @@ def _products(dev, A, nr, nc, seed):
     return out
 
 
+def _oracle_products(nr, nc, Ap, Aj, Ax, seed):
+    """_products' four products from the oracle, same vectors, same order"""
+    import oracle as O
+    rng = np.random.default_rng(seed)
+    xh, yh = rng.uniform(-1, 1, nc), rng.uniform(-1, 1, nr)
+    A = O.CSR(nr, Ap, Aj, Ax)
+    return [O.spmv(2, A, xh, 1.25, -0.75, z=yh.copy()), O.spmv(3, A, xh, -0.375, 1.5, yh),
+            O.spmv(1, A, xh, -2.5), O.spmv(0, A, xh)]
+
+
 @pytest.mark.parametrize("name", ["p5_6", "p7_4", "band255", "band256", "rnd400x9", "scattered40k", "rect_37x53",
                                   "one_row", "nnz0"])
 def test_from_device_equals_upload(dev, name):
@@ -216,8 +227,11 @@ def test_from_device_equals_upload(dev, name):
     elif expect == "plain":
         assert fd.ndiag == 0 and not fd.windowed
     if nr:
-        for a, b in zip(_products(dev, fd, nr, nc, 5), _products(dev, up, nr, nc, 5)):
-            assert same(a, b)
+        # both handles come from one builder, so each is also held to the oracle's products
+        want = _oracle_products(nr, nc, Ap, Aj, Ax, 5)
+        for q, (a, b, o) in enumerate(zip(_products(dev, fd, nr, nc, 5), _products(dev, up, nr, nc, 5), want)):
+            assert same(a, b), q
+            assert same(a, o) and same(b, o), q
     fd.close()
     up.close()
 

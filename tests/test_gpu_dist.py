@@ -348,6 +348,60 @@ def test_dist_upload_bad_input_fails_on_every_rank(bad_rank):
     assert all(p.exitcode == 0 for p in procs)
 
 
+def _codes_worker(rank, world, port, N, seed, out):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import lssp_amd
+        from inputs import uniform
+        from lssp_amd.dist import GlooTransport
+        dev = lssp_amd.Device(0)
+        dev.comm_init_host(world, rank, GlooTransport())
+        n = N ** 3
+        blk = (n + world - 1) // world
+        r0 = min(rank * blk, n)
+        nl = min(blk, n - r0)
+        Ap, Aj, Ax = lssp_amd.poisson(3, N, r0, nl)
+        A = lssp_amd.DMat(dev, Ap, Aj, Ax, dist=(n, r0))
+        xv = dev.vec(A.nx, np.concatenate([uniform(seed, n)[r0:r0 + nl], np.zeros(A.nhalo)]))
+        yv = dev.vec(A.nx)
+        A.mv_mxy(xv, yv)
+        out.put((rank, (A.nhalo, A.ndiag, A.rowcodes, A.valcodes, yv.download(nl))))
+        dev.barrier()
+        dev.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_dist_upload_codings_two_ranks():
+    """The codings of a distributed upload (build_codings' distributed branch): two z-slabs
+    of the 7-pt 8^3 box, so each rank has halo columns.  Every rank is offset- and
+    row-coded, none is value-coded (constant coefficients: a one-rank handle would be),
+    and the product is the oracle's."""
+    import torch.multiprocessing as mp
+    from inputs import uniform
+    N, seed = 8, 0xC0DE
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_codes_worker, args=(r, 2, port, N, seed, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        got = dict(q.get(timeout=120) for _ in range(2))
+    finally:
+        for p in procs:
+            p.join(timeout=30)
+    assert all(p.exitcode == 0 for p in procs)
+    for rank in range(2):
+        nhalo, ndiag, rowcodes, valcodes, _ = got[rank]
+        assert nhalo == N * N and ndiag > 0 and rowcodes > 0 and valcodes == 0, (rank, got[rank][:4])
+    A = O.poisson(3, N)
+    assert np.array_equal(np.concatenate([got[0][4], got[1][4]]), O.spmv(0, A, uniform(seed, A.n)))
+
+
 def test_rccl_one_rank_transport_selftest():
     """The RCCL branch of the transport on one GPU: a real 1-rank communicator
     (lssp_amd_comm_init with nranks = 1), then lssp_amd_comm_selftest drives

@@ -214,27 +214,46 @@ def test_eligibility_edges(dev, which):
         masks[44] = 511
     nr, nc, Ap, Aj, Ax = subsets(masks)
     D = lssp_amd.DMat(dev, Ap, Aj, Ax, ncols=nc)
-    assert D.ndiag == 9
+    assert D.ndiag == 9  # the layer below a refusal is intact
     assert D.rowcodes == (256 if which == "max_patterns" else 0)
+    if D.rowcodes == 0:
+        assert D.valcodes == 0
     for q, (a, o) in enumerate(zip(products(dev, D, nr, nc), oracle_products(Ap, Aj, Ax, nr, nc))):
         assert same(a, o), q
     D.close()
 
 
-def test_255_offsets(dev):
-    """255 distinct offsets, three per row (the band of test_gpu_assemble.py): ids up to 254 in
-    the pattern keys, whichever mode the pattern count gives the matrix"""
-    import lssp_amd
-    n, noff = 600, 255
+def band(noff, n=600):
+    """n rows whose entries use exactly noff distinct offsets, three per row (the band of
+    test_gpu_assemble.py)"""
     lo = -(noff // 2)
     rows = [[i + o for o in sorted({lo + (3 * i + t) % noff for t in range(3)}) if 0 <= i + o < n] for i in range(n)]
     Ap = np.zeros(n + 1, np.int32)
     np.cumsum([len(r) for r in rows], out=Ap[1:])
     Aj = np.asarray([c for r in rows for c in r], np.int32)
     assert np.unique(Aj - np.repeat(np.arange(n), np.diff(Ap))).size == noff
-    Ax = np.random.default_rng(1).uniform(-1, 1, Aj.size)
+    return n, Ap, Aj, np.random.default_rng(1).uniform(-1, 1, Aj.size)
+
+
+def test_255_offsets(dev):
+    """255 distinct offsets: ids up to 254 in the pattern keys, whichever mode the pattern
+    count gives the matrix"""
+    import lssp_amd
+    n, Ap, Aj, Ax = band(255)
     D = lssp_amd.DMat(dev, Ap, Aj, Ax)
     assert D.ndiag == 255 and 0 <= D.rowcodes <= 256
+    for q, (a, o) in enumerate(zip(products(dev, D, n, n), oracle_products(Ap, Aj, Ax, n, n))):
+        assert same(a, o), q
+    D.close()
+
+
+def test_256_offsets(dev):
+    """a 256th distinct offset, the offset layer's refusal: no ids, so neither row nor value
+    codes, and the products of the plain CSR"""
+    import lssp_amd
+    n, Ap, Aj, Ax = band(256)
+    D = lssp_amd.DMat(dev, Ap, Aj, Ax)
+    assert (D.ndiag, D.rowcodes, D.valcodes) == (0, 0, 0)
     for q, (a, o) in enumerate(zip(products(dev, D, n, n), oracle_products(Ap, Aj, Ax, n, n))):
         assert same(a, o), q
     D.close()

@@ -149,7 +149,7 @@ def test_eligibility_edges(dev, nvals):
     nr, nc, Ap, Aj, Ax = banded(nvals)
     assert np.unique(Ax.reshape(nr, 3), axis=0).shape[0] == nvals
     D = lssp_amd.DMat(dev, Ap, Aj, Ax, ncols=nc)
-    assert D.rowcodes == 1
+    assert D.ndiag == 3 and D.rowcodes == 1  # the layers below a refusal are intact
     assert D.valcodes == (ROWVAL_MAX if nvals == ROWVAL_MAX else 0)
     check_products(dev, D, Ap, Aj, Ax, nr, nc)
     D.close()
