@@ -11,7 +11,7 @@
 #include <mutex>
 #include <thread>
 
-#include "bilu_dev.h"
+#include "iluk_refactor_dev.h"
 #include "internal.h"
 
 using namespace lssp_amd;
@@ -69,6 +69,9 @@ static void copy_factors(lssp_amd_ilu *M, int n, const int *Lp, const int *Lj, c
     M->Uj.assign(Uj, Uj + Up[n]);
     M->Ux.assign(Ux, Ux + Up[n]);
 }
+
+// a plan's factored F as the line refills read it: both sweeps' view, L's diagonal the unit
+static FactorView plan_view(const RefactorPlan &p) { return FactorView{p.d_Fp, p.d_Fj, p.d_Fx, p.d_dpos, true}; }
 
 // the device creates' public prologue: *out cleared, then the arguments; any_kind: ILUK or ILUT
 static int check_create_dev_args(lssp_amd_ctx *c, const lssp_amd_mat *A, bool any_kind, int kind, lssp_amd_ilu **out)
@@ -308,7 +311,7 @@ int lssp_amd_ilu_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat *
         M->host_stale = true;
         if (setup_times_on()) LSSP_HIP(hipStreamSynchronize(c->stream));
         clk.mark("numeric ILU(0)");
-        LSSP_TRY(launch_line_refill(c, M->line, M->n, M->rf->d_Fp, M->rf->d_Fj, M->rf->d_Fx));
+        LSSP_TRY(launch_line_refill(c, M->line, M->n, plan_view(*M->rf), plan_view(*M->rf)));
         LSSP_HIP(hipStreamSynchronize(c->stream));
         clk.mark("coefficient streams");
         if (setup_times_on())  // the refill's traffic: each sweep reads F once and writes every slot of its stream
@@ -367,7 +370,7 @@ int lssp_amd_iluk_refactor(lssp_amd_ctx *c, lssp_amd_ilu *M, const lssp_amd_mat 
             LSSP_TRY(launch_pk6_refill_scalar(c, M->upper, true, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx, p.d_flag));
             LSSP_HIP(hipMemcpyAsync(&nonunit, p.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         } else {
-            LSSP_TRY(launch_linefill_refill(c, M->line, M->n, p.d_Fp, p.d_Fj, p.d_dpos, p.d_Fx));
+            LSSP_TRY(launch_linefill_refill(c, M->line, M->n, plan_view(p), plan_view(p)));
         }
         LSSP_HIP(hipStreamSynchronize(c->stream));
         if (packets) M->upper.bp_unit = nonunit ? 0 : 1;
@@ -438,7 +441,7 @@ static int ilu_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, int 
         LSSP_TRY(clk.mark("numeric ILU(0)"));
         LSSP_TRY(build_line_sweep_box(c, (int)nx, (int)ny, (int)nz, M->line));
         LSSP_TRY(clk.mark("allocation + zeroing"));
-        LSSP_TRY(launch_line_refill(c, M->line, n, M->rf->d_Fp, M->rf->d_Fj, M->rf->d_Fx));
+        LSSP_TRY(launch_line_refill(c, M->line, n, plan_view(*M->rf), plan_view(*M->rf)));
         LSSP_HIP(hipStreamSynchronize(c->stream));
         LSSP_TRY(clk.mark("coefficient streams"));
         // what ilu_upload's level passes report: row (i, j, k) is on level i + j + k of
@@ -495,7 +498,7 @@ static int iluk1_create_dev(lssp_amd_ctx *c, const lssp_amd_mat *A, int kind, in
         LSSP_TRY(clk.mark("numeric"));
         LSSP_TRY(build_linefill_box(c, (int)nx, (int)ny, (int)nz, M->line));
         LSSP_TRY(clk.mark("allocation"));
-        LSSP_TRY(launch_linefill_refill(c, M->line, n, M->rf->d_Fp, M->rf->d_Fj, M->rf->d_dpos, M->rf->d_Fx));
+        LSSP_TRY(launch_linefill_refill(c, M->line, n, plan_view(*M->rf), plan_view(*M->rf)));
         LSSP_HIP(hipStreamSynchronize(c->stream));
         LSSP_TRY(clk.mark("refill"));
         // what ilu_upload's level passes report: row (i, j, k) is on level i + 2 j + 3 k

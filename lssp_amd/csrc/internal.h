@@ -623,7 +623,8 @@ int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const s
 int line_rearm(lssp_amd_ctx *c, LineILU &li);
 // lssp_amd_ilu_create_dev: the tiled sweeps of the ILU(0) of a complete nx x ny
 // x nz box from the grid alone -- build_line_sweep's tiles, layouts and buffers,
-// the coefficient streams zeroed for launch_line_refill.  line_box_tiled:
+// the coefficient streams zeroed for launch_line_refill, which every create
+// (build_line_sweep included) takes its values from.  line_box_tiled:
 // build_line_sweep would put that factor on the 16 x 8 tiles (not on the
 // one-workgroup route, not switched off); else EUNSUPPORTED.
 bool line_box_tiled(int nx, int ny, int nz);
@@ -644,7 +645,7 @@ int build_linefill_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li);
 // What the two tiled builds share (linesweep.hip).  line_layout, from a sweep's
 // tiles (ls.P / NJ / LV set; W tiles per tile row): every tile's place in the
 // streams, the tile table, the claim counter, the coefficient stream's
-// allocation (line_coef_len doubles; its values per kind) and the claim order
+// allocation (line_coef_len doubles; its values are the refill kernels') and the claim order
 // -- tile (J, K) by ascending wj J + wk K, its earliest start, so both producers
 // of a tile are claimed before it.  finish_line_tiles, after both layouts: the
 // L tiles' links to their mirror U tiles, both rhs streams (zeroed), the
@@ -677,10 +678,12 @@ int line_launch(lssp_amd_ctx *c, const LineSweep &ls, const LineArgs &a, LineKer
 int launch_linef_gather(lssp_amd_ctx *c, const LineSweep &ls, int mirror, const double *rhs, double *stream);
 int launch_linef(lssp_amd_ctx *c, const LineILU &li, int which, const double *stream, double *out, int outk,
                  const LineTail *tail = nullptr);
-// small 2-D grids on one workgroup (linefill.hip): cl / cu hold the L / U rows in
-// sweep order, components S, (SE,) W (, diag); mode 0 apply, 1 L, 2 U
-int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const std::vector<double> &cl,
-                const std::vector<double> &cu, LineILU &li);
+// small 2-D grids on one workgroup (linefill.hip): L / U are views of the host
+// factors, each row's ncl (U: 3, fill 4) components S, (SE,) W (, diag) taken
+// by the shared row rules (iluk_refactor_dev.h); mode 0 apply, 1 L, 2 U
+struct FactorView;
+int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const FactorView &L, const FactorView &U,
+                LineILU &li);
 int launch_lineg(lssp_amd_ctx *c, const LineILU &li, int mode, double *x, const double *rhs);
 constexpr int G2_MAXNY = 256;  // k_lineg: lines (lanes) of one workgroup
 // k_lineg addresses its streams and output through buffer resources: every
@@ -713,10 +716,9 @@ int refactor_levels(lssp_amd_ctx *c, RefactorPlan &p, int n);
 // of those pivots is not exactly 1.0
 int launch_pk6_refill_scalar(lssp_amd_ctx *c, const TriSched &t, bool upper, int n, const int *Fp, const int *Fj,
                              const int *dpos, const double *Fx, int *nonunit = nullptr);
-// linefill.hip: both coefficient streams of a k_linef factor rewritten from
-// the factored values Fx on the pattern (Fp, Fj); every slot is written
-int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const int *dpos,
-                           const double *Fx);
+// linefill.hip: both coefficient streams of a k_linef factor written from one
+// factor view per sweep (iluk_refactor_dev.h); every slot is written
+int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const FactorView &fl, const FactorView &fu);
 // lssp_amd_ilu_create_dev (ilu_factor.hip), for a device CSR (n rows, nnz
 // entries) and a box nx x ny x nz = n.  box_pattern_check: *ok = the pattern is
 // exactly the complete natural-order 5-/7-point stencil of that box, rows
@@ -778,9 +780,16 @@ int iluk_split_pattern_dev(lssp_amd_ctx *c, int n, const RefactorPlan &p, IlutDe
 int iluk_split_values_dev(lssp_amd_ctx *c, int n, const RefactorPlan &p, const IlutDevFactors &S);
 void iluk_split_free(IlutDevFactors *S);
 int iluk_plan_levels_dev(lssp_amd_ctx *c, int n, RefactorPlan &p, const IlutDevFactors &S);
-// linesweep.hip: both coefficient streams of a k_line2 factor rewritten from
-// the factored values Fx on the pattern (Fp, Fj); every slot is written
-int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx);
+// linesweep.hip: both coefficient streams of a k_line2 factor written from one
+// factor view per sweep (iluk_refactor_dev.h: the combined F for both, or a
+// lone L and a lone U); every slot is written.  line_refill_host: the same for
+// a host create of either kind -- L, then U, each through temporary device
+// buffers and refill, its kind's one-sweep launch (which: 0 L, 1 U).
+int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const FactorView &fl, const FactorView &fu);
+using LineSweepRefill = int (*)(lssp_amd_ctx *, LineILU &, int which, long n, const FactorView &);
+int line_refill_host(lssp_amd_ctx *c, LineILU &li, long n, const std::vector<int> &Lp, const std::vector<int> &Lj,
+                     const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
+                     const std::vector<double> &Ux, LineSweepRefill refill);
 int launch_line_apply(lssp_amd_ctx *c, const LineILU &li, double *x, const double *rhs);
 // the apply followed by z = op(A x) (+ fused dots), the product run by the U
 // sweep's workgroups as planes of x become final (k_line2 tail); results are

@@ -196,31 +196,6 @@ bool detect_fill1(int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
     return true;
 }
 
-// coefficients of one sweep in its row order (r_sweep = r for L, n-1-r for U):
-// {B, BE, BN, S, SE, W(, diag)}; a missing neighbour gets +0.0
-struct FillCoef {
-    std::vector<double> c;
-    int NA = 6;
-    void build(const std::vector<int> &Tp, const std::vector<int> &Tj, const std::vector<double> &Tx, bool upper,
-               long n, long nx, long pl, int na)
-    {
-        NA = na;
-        c.assign((size_t)n * NA, 0.0);
-        parallel_for(n, [&](long r0, long r1) {
-            for (long r = r0; r < r1; r++) {
-                double *row = c.data() + (size_t)(upper ? n - 1 - r : r) * NA;
-                const int b = Tp[r], e = Tp[r + 1];
-                if (NA == 7) row[6] = upper ? Tx[b] : Tx[e - 1];
-                for (int q = upper ? b + 1 : b; q < (upper ? e : e - 1); q++) {
-                    const long off = upper ? Tj[q] - r : r - Tj[q];
-                    const int a = off == pl ? 0 : off == pl - 1 ? 1 : off == pl - nx ? 2 : off == nx ? 3 : off == nx - 1 ? 4 : 5;
-                    row[a] = Tx[q];
-                }
-            }
-        });
-    }
-};
-
 // mirror-symmetric widths (<= 16) of the j' = j + k columns, m = ny + nz - 1
 std::vector<int> fill_widths(int m)
 {
@@ -242,34 +217,6 @@ int fill_T(int nx, int nj, int np)
     return (T + lf::LV - 1) / lf::LV * lf::LV;
 }
 
-// the coefficient stream of a laid-out sweep (line_layout) from the host factors
-int fill_upload(const LineGeom &g, const FillCoef &src, LineSweep &ls)
-{
-    using namespace lf;
-    const int nx = g.nx, NA = ls.NA;
-    const std::vector<LineTile> &tt = ls.h_tiles;
-    std::vector<double> coef(line_coef_len(ls), 0.0);
-    parallel_for((long)tt.size(), [&](long t0, long t1) {
-        for (long ti = t0; ti < t1; ti++) {
-            const LineTile &t = tt[ti];
-            for (int p = 0; p < t.np; p++)
-                for (int l = 0; l < t.nj; l++) {
-                    const int j = t.j0 + l - (t.k0 + p);
-                    if (j < 0 || j >= g.ny) continue;
-                    const int off = 2 * l + p + sig(p);
-                    for (int i = 0; i < nx; i++) {
-                        const long v = i + off;
-                        const long r = ((long)(t.k0 + p) * g.ny + j) * nx + i;
-                        double *dst = coef.data() + (size_t)(t.cbase + v * P * t.nj + p * t.nj + l) * NA;
-                        for (int a = 0; a < NA; a++) dst[a] = src.c[(size_t)r * NA + a];
-                    }
-                }
-        }
-    });
-    LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
-    return LSSP_AMD_OK;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -284,28 +231,35 @@ int fill_upload(const LineGeom &g, const FillCoef &src, LineSweep &ls)
 // word and one barrier -- no hand-offs between CUs.  The tiled sweeps put one
 // plane per tile on 16 of 128 lanes and chain the tiles of a 2-D grid through
 // cross-CU hand-offs for the same levels.  Streams, level-major: [v][S, (SE,)
-// W, (diag,) rhs][lane] (rows off the grid +0.0), the coefficients at build,
+// W, (diag,) rhs][lane] (rows off the grid +0.0), the coefficients at build --
+// the layout is k_lineg's own and the grids are tiny, so the host fills it, each
+// row's components from the shared row rule (line_coef_row / linef_coef_row:
+// the last NC of a row's NA, after c_k or B, BE, BN) on the host factors --
 // the rhs per apply (k_lineg_rhs gathers the first sweep's; the L sweep writes
 // the U sweep's); each wave LDS-DMAs its pieces G2_D levels ahead into a ring.
 // ---------------------------------------------------------------------------
-int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const std::vector<double> &cl,
-                const std::vector<double> &cu, LineILU &li)
+int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const FactorView &L, const FactorView &U,
+                LineILU &li)
 {
     const int nx = g.nx, ny = g.ny, NYP = (ny + 63) / 64 * 64, sk = fill ? 2 : 1, V = nx + sk * (ny - 1);
     const int ncu = fill ? 4 : 3;
     const int NW = NYP / 64;
-    auto make = [&](const std::vector<double> &src, int NC) {
+    const long n = (long)nx * ny;
+    auto make = [&](const FactorView &f, bool upper, int NC) {
         std::vector<double> st((size_t)V * (NC + 1) * NYP + 128, 0.0);  // (+1 KB: whole DMA pieces)
+        const int skip = fill ? 3 : 1, NA = skip + NC;
         for (int v = 0; v < V; v++)
             for (int j = 0; j < ny; j++) {
                 const int i = v - sk * j;
                 if (i < 0 || i >= nx) continue;
-                const double *cr = src.data() + ((size_t)j * nx + i) * NC;  // (sweep order: U mirrored)
-                for (int k = 0; k < NC; k++) st[g2_at(v, NW, NC, k, j)] = cr[k];
+                double cr[7];  // (sweep order: U mirrored)
+                if (fill) linef_coef_row((long)j * nx + i, upper, n, nx, n, NA, f, cr);
+                else line_coef_row((long)j * nx + i, upper, n, nx, n, NA, f, cr);
+                for (int k = 0; k < NC; k++) st[g2_at(v, NW, NC, k, j)] = cr[skip + k];
             }
         return st;
     };
-    const std::vector<double> sl = make(cl, ncl), su = make(cu, ncu);
+    const std::vector<double> sl = make(L, false, ncl), su = make(U, true, ncu);
     LSSP_HIP(hipMalloc(&li.d_g2L, sizeof(double) * sl.size()));
     LSSP_HIP(hipMemcpy(li.d_g2L, sl.data(), sizeof(double) * sl.size(), hipMemcpyHostToDevice));
     LSSP_HIP(hipMalloc(&li.d_g2U, sizeof(double) * su.size()));
@@ -330,9 +284,9 @@ int build_lineg(lssp_amd_ctx *c, const LineGeom &g, int fill, int ncl, const std
 // skewed columns' widths, the L tiles and their mirrored U tiles, the tiles off
 // the grid, both stream layouts, claim counters and order, the rhs streams
 // (zeroed) and the armed hand-off buffers.  The coefficient streams are
-// allocated here; cl / cu (host factors) fill them, or, both nullptr, they are
-// zeroed on the context's stream for launch_linefill_refill to write.
-static int build_linefill_tiles(lssp_amd_ctx *c, const LineGeom &g, const FillCoef *cl, const FillCoef *cu, LineILU &li)
+// allocated here and zeroed on the context's stream (the loaders' slack stays
+// +0.0); k_linef_refill writes their values.
+static int build_linefill_tiles(lssp_amd_ctx *c, const LineGeom &g, LineILU &li)
 {
     using namespace lf;
     const int m = g.ny + g.nz - 1;
@@ -412,18 +366,15 @@ static int build_linefill_tiles(lssp_amd_ctx *c, const LineGeom &g, const FillCo
     // levels, a k-hop ~np + 1 + 4
     LSSP_TRY(line_layout(c, g, Lt, NAL, W, 2 * NJ + 4, P + 5, li.L));
     LSSP_TRY(line_layout(c, g, Ut, 7, W, 2 * NJ + 4, P + 5, li.U));
-    if (cl && cu) {
-        LSSP_TRY(fill_upload(g, *cl, li.L));
-        LSSP_TRY(fill_upload(g, *cu, li.U));
-    } else {
-        LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * line_coef_len(li.L), c->stream));
-        LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * line_coef_len(li.U), c->stream));
-    }
+    LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * line_coef_len(li.L), c->stream));
+    LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * line_coef_len(li.U), c->stream));
     // hand-off rows: every step the poller may address (steps up to TS + DH + 1,
     // two rows each, + HJ0), HKS k entries and P j entries each
     const long rows = std::max(li.L.tmax, li.U.tmax) + 32;
     return finish_line_tiles(c, li, rows * HKS, rows * P);
 }
+
+static int linefill_refill_sweep(lssp_amd_ctx *c, LineILU &li, int which, long n, const FactorView &f);
 
 int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
                    const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
@@ -431,21 +382,12 @@ int build_linefill(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std
 {
     LineGeom g;
     if (!detect_fill1(n, Lp, Lj, Lx, Up, Uj, g)) return LSSP_AMD_EUNSUPPORTED;
-    const long pl = (long)g.nx * g.ny;
-    FillCoef cl, cu;
-    cl.build(Lp, Lj, Lx, false, n, g.nx, pl, g.unitL ? 6 : 7);
-    cu.build(Up, Uj, Ux, true, n, g.nx, pl, 7);
     if (fill1_lineg_route(g)) {
-        // k_lineg's components: S, SE, W (, diag) = FillCoef's 3, 4, 5 (, 6)
-        const int ncl = g.unitL ? 3 : 4;
-        std::vector<double> sl((size_t)n * ncl), su((size_t)n * 4);
-        for (long r = 0; r < n; r++) {
-            for (int k = 0; k < ncl; k++) sl[r * ncl + k] = cl.c[r * cl.NA + 3 + k];
-            for (int k = 0; k < 4; k++) su[r * 4 + k] = cu.c[r * cu.NA + 3 + k];
-        }
-        return build_lineg(c, g, 1, ncl, sl, su, li);
+        const FactorView L{Lp.data(), Lj.data(), Lx.data(), nullptr, false}, U{Up.data(), Uj.data(), Ux.data(), nullptr, false};
+        return build_lineg(c, g, 1, g.unitL ? 3 : 4, L, U, li);
     }
-    return build_linefill_tiles(c, g, &cl, &cu, li);
+    LSSP_TRY(build_linefill_tiles(c, g, li));
+    return line_refill_host(c, li, n, Lp, Lj, Lx, Up, Uj, Ux, linefill_refill_sweep);
 }
 
 // lssp_amd_iluk_create_dev: build_linefill would put the ILU(1) of the complete
@@ -463,7 +405,7 @@ int build_linefill_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li)
     if (!linefill_box_tiled(nx, ny, nz)) return LSSP_AMD_EUNSUPPORTED;
     LineGeom g;
     fill1_box_geom(nx, ny, nz, g);
-    return build_linefill_tiles(c, g, nullptr, nullptr, li);
+    return build_linefill_tiles(c, g, li);
 }
 
 // ---------------------------------------------------------------------------
@@ -1132,17 +1074,15 @@ int launch_linef(lssp_amd_ctx *c, const LineILU &li, int which, const double *st
     return ls.NA == 6 ? linef_launch_t<6, 1>(c, ls, a) : linef_launch_t<7, 1>(c, ls, a);
 }
 
-// lssp_amd_iluk_refactor: FillCoef::build + fill_upload on the device.  Workgroup
+// The coefficient streams of the k_linef sweeps, from factors in HBM.  Workgroup
 // (x, tile): 256 consecutive slots of the tile's T * P * nj, one per lane.  A
 // lane finds its slot's sweep row (linef_slot_row), gathers that row's NA
-// coefficients from the factored values (linef_coef_row; +0.0 for a slot off
+// coefficients from the sweep's factor view (linef_coef_row; +0.0 for a slot off
 // the grid and for a missing neighbour) into LDS, and the workgroup then stores
 // the 256 * NA doubles in stream order, consecutive lanes to consecutive
 // addresses.  Every slot of every tile is written, skipped tiles included.
 __global__ __launch_bounds__(256) void k_linef_refill(const LineTile *__restrict__ tiles, int ntiles, int NA, int upper,
-                                                      int nx, int ny, long n, const int *__restrict__ Fp,
-                                                      const int *__restrict__ Fj, const int *__restrict__ dpos,
-                                                      const double *__restrict__ Fx, double *__restrict__ coef)
+                                                      int nx, int ny, long n, FactorView f, double *__restrict__ coef)
 {
     __shared__ double sm[256 * 7];
     const long pl = (long)nx * ny;
@@ -1154,7 +1094,7 @@ __global__ __launch_bounds__(256) void k_linef_refill(const LineTile *__restrict
             double *mine = sm + threadIdx.x * NA;
             if (s < slots) {
                 const long rs = linef_slot_row(s, d.j0, d.nj, d.k0, d.np, nx, ny);
-                if (rs >= 0 && rs < n) linef_coef_row(rs, upper != 0, n, nx, pl, NA, Fp, Fj, dpos, Fx, mine);
+                if (rs >= 0 && rs < n) linef_coef_row(rs, upper != 0, n, nx, pl, NA, f, mine);
                 else
                     for (int a = 0; a < NA; a++) mine[a] = 0.0;
             }
@@ -1167,22 +1107,25 @@ __global__ __launch_bounds__(256) void k_linef_refill(const LineTile *__restrict
     }
 }
 
-int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const int *dpos,
-                           const double *Fx)
+// one sweep's stream (which: 0 L, 1 U) from its factor view
+static int linefill_refill_sweep(lssp_amd_ctx *c, LineILU &li, int which, long n, const FactorView &f)
 {
     if (li.kind != 1 || li.g2 || li.ntiles <= 0) return LSSP_AMD_EUNSUPPORTED;
-    static_assert(lf::P == LINEF_P, "iluk_refactor_dev.h restates the tile's planes");
-    for (int which = 0; which < 2; which++) {
-        const LineSweep &ls = which ? li.U : li.L;
-        if ((long)ls.nx * ls.ny * ls.nz != n || (ls.NA != 6 && ls.NA != 7)) return LSSP_AMD_EINVAL;
-        const long maxslots = (long)ls.tmax * lf::P * lf::NJ;
-        const dim3 grid((unsigned)std::min<long>((maxslots + 255) / 256, 1024), (unsigned)std::min(ls.ntiles, 65535));
-        k_linef_refill<<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.ntiles, ls.NA, which, ls.nx, ls.ny, n, Fp, Fj, dpos,
-                                                    Fx, ls.d_coef);
-        LSSP_HIP(hipGetLastError());
-    }
+    static_assert(lf::P == LINEF_P, "iluk_refactor_dev.h states the tile's planes");
+    const LineSweep &ls = which ? li.U : li.L;
+    if ((long)ls.nx * ls.ny * ls.nz != n || (ls.NA != 6 && ls.NA != 7)) return LSSP_AMD_EINVAL;
     li.lstream_of = nullptr;
+    const long maxslots = (long)ls.tmax * lf::P * lf::NJ;
+    const dim3 grid((unsigned)std::min<long>((maxslots + 255) / 256, 1024), (unsigned)std::min(ls.ntiles, 65535));
+    k_linef_refill<<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.ntiles, ls.NA, which, ls.nx, ls.ny, n, f, ls.d_coef);
+    LSSP_HIP(hipGetLastError());
     return LSSP_AMD_OK;
+}
+
+int launch_linefill_refill(lssp_amd_ctx *c, LineILU &li, long n, const FactorView &fl, const FactorView &fu)
+{
+    LSSP_TRY(linefill_refill_sweep(c, li, 0, n, fl));
+    return linefill_refill_sweep(c, li, 1, n, fu);
 }
 
 }  // namespace lssp_amd

@@ -40,7 +40,8 @@
 // in order per wave) belongs to one role with one lead, so no wait ever covers
 // another role's slow operations.
 //
-// Layouts (host, build_line_sweep): per tile, per step, per plane, the rows
+// Layouts (line_layout; the values: k_coef_refill, for every create and
+// refactor, by the row rules of iluk_refactor_dev.h): per tile, per step, per plane, the rows
 // valid at that step (a contiguous lane range [lo, hi]), each row's NA
 // coefficients {c_k, c_j, c_i(, diag)} together; steps padded to an even row
 // count (16-byte blocks).  The L sweep writes its output into the U
@@ -57,6 +58,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "iluk_refactor_dev.h"
 #include "internal.h"
 #include "linesweep_dev.h"
 
@@ -126,51 +128,6 @@ static bool detect_grid(int n, const std::vector<int> &Lp, const std::vector<int
     return true;
 }
 
-// k_line2's plane skew: compute wave w owns planes 4w .. 4w+3 and runs
-// (LV-1) w levels later, so the k-input of a wave's first plane is one whole
-// step (LV levels) old
-static inline int line_sigma(int LV, int p) { return (LV - 1) * (p / 4); }
-
-// rows of a tile (nj lines, np planes) valid at level s, plane p: lanes [lo, hi]
-// (row i = s - l - p - sigma(p))
-static inline void step_range(int nx, int nj, int np, int s, int p, int sg, int &lo, int &hi)
-{
-    if (p >= np) {
-        lo = 0;
-        hi = -1;
-        return;
-    }
-    lo = std::max(0, s - p - sg - nx + 1);
-    hi = std::min(nj - 1, s - p - sg);
-}
-
-// coefficients of one sweep in that sweep's row order (row r_sweep = r for L,
-// n-1-r for U), NA per row: component a = 0 (k-1), 1 (j-1), 2 (i-1), 3
-// (diagonal); a missing neighbour gets +0.0 (its operand is +0.0 too)
-struct CoefSrc {
-    std::vector<double> c;
-    int NA = 3;
-    void build(const std::vector<int> &Tp, const std::vector<int> &Tj, const std::vector<double> &Tx, bool upper,
-               long n, long nx, long plane, int na)
-    {
-        NA = na;
-        c.assign((size_t)n * NA, 0.0);
-        parallel_for(n, [&](long r0, long r1) {
-        for (long r = r0; r < r1; r++) {
-            double *row = c.data() + (size_t)(upper ? n - 1 - r : r) * NA;
-            const int b = Tp[r], e = Tp[r + 1];
-            if (NA == 4) row[3] = upper ? Tx[b] : Tx[e - 1];
-            for (int q = upper ? b + 1 : b; q < (upper ? e : e - 1); q++) {
-                const long off = upper ? Tj[q] - r : r - Tj[q];
-                const int a = off == plane ? 0 : off == nx ? 1 : 2;  // detect_grid: off is one of 1, nx, plane
-                row[a] = Tx[q];
-            }
-        }
-        });
-    }
-    double get(long r_sweep, int a) const { return c[(size_t)r_sweep * NA + a]; }
-};
-
 static int build_tiles(const LineGeom &g, int P, int NJ, int LV, int W, std::vector<LineTile> &tiles, int &S)
 {
     (void)NJ;
@@ -217,8 +174,7 @@ constexpr long STREAM_SLACK = 16 * 1024 / 8;
 size_t line_coef_len(const LineSweep &ls) { return (size_t)ls.rows_total * ls.NA + STREAM_SLACK; }
 
 // The part of a sweep (either kind) that depends on the grid alone (internal.h);
-// the coefficient stream's values: upload_sweep / fill_upload from host
-// factors, or zeroed for k_coef_refill / k_linef_refill.
+// the coefficient stream's values are k_coef_refill's / k_linef_refill's.
 int line_layout(lssp_amd_ctx *, const LineGeom &g, const std::vector<LineTile> &tiles, int NA, int W, int wj, int wk,
                 LineSweep &ls)
 {
@@ -296,35 +252,6 @@ int finish_line_tiles(lssp_amd_ctx *c, LineILU &li, long hk_stride, long hj_stri
     return LSSP_AMD_OK;
 }
 
-// the coefficient stream of a laid-out sweep from the host factors
-static int upload_sweep(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc &src, LineSweep &ls)
-{
-    const int nx = g.nx, P = ls.P, LV = ls.LV, NA = ls.NA;
-    const std::vector<LineTile> &tt = ls.h_tiles;
-    std::vector<double> coef(line_coef_len(ls), 0.0);
-    parallel_for((long)tt.size(), [&](long t0, long t1) {
-    for (long ti = t0; ti < t1; ti++) {
-        const LineTile &t = tt[ti];
-        for (int s = 0; s < t.T; s++) {
-            double *blk = coef.data() + (size_t)(t.cbase + (long)s * P * t.nj) * NA;
-            for (int p = 0; p < t.np; p++) {
-                int lo, hi;
-                const int sg = line_sigma(LV, p);
-                step_range(nx, t.nj, t.np, s, p, sg, lo, hi);
-                for (int l = lo; l <= hi; l++) {
-                    const long i = s - l - p - sg;
-                    const long r = ((long)(t.k0 + p) * g.ny + (t.j0 + l)) * nx + i;
-                    for (int a = 0; a < NA; a++) blk[(size_t)(p * t.nj + l) * NA + a] = src.get(r, a);
-                }
-            }
-        }
-    }
-    });
-    LSSP_HIP(hipMemcpy(ls.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
-    (void)c;
-    return LSSP_AMD_OK;
-}
-
 // tiles of k_line2: 8 planes x 16 lines, two levels per workgroup step (round 3's
 // k_line -- 256 rows and one level per step, 64 x 4 / 32 x 8 / 16 x 16 tiles --
 // was removed in round 6 after two rounds as an A/B option only)
@@ -355,10 +282,9 @@ static bool lineg_route(const LineGeom &g)
 // Everything of the tiled k_line2 sweeps that the grid alone decides: the L
 // tiles and their mirrored U tiles, both stream layouts, claim counters and
 // order, the rhs streams (zeroed) and the armed hand-off buffers.  The
-// coefficient streams are allocated here; cl / cu (host factors) fill them, or,
-// both nullptr, they are zeroed on the context's stream for
-// launch_line_refill to write.
-static int build_line_tiles(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc *cl, const CoefSrc *cu, LineILU &li)
+// coefficient streams are allocated here and zeroed on the context's stream
+// (the loaders' slack stays +0.0); k_coef_refill writes their values.
+static int build_line_tiles(lssp_amd_ctx *c, const LineGeom &g, LineILU &li)
 {
     int P, NJ, LV;
     line_plan(g, P, NJ, LV);
@@ -397,17 +323,14 @@ static int build_line_tiles(lssp_amd_ctx *c, const LineGeom &g, const CoefSrc *c
     LineGeom gu = g;
     for (int k = 0; k < g.nz; k++) gu.kin[k] = k > 0 ? g.kin[g.nz - k] : 0;
     LSSP_TRY(line_layout(c, gu, Ut, NAD, W, 1, 1, li.U));
-    if (cl && cu) {
-        LSSP_TRY(upload_sweep(c, g, *cl, li.L));
-        LSSP_TRY(upload_sweep(c, gu, *cu, li.U));
-    } else {
-        LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * line_coef_len(li.L), c->stream));
-        LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * line_coef_len(li.U), c->stream));
-    }
+    LSSP_HIP(hipMemsetAsync(li.L.d_coef, 0, sizeof(double) * line_coef_len(li.L), c->stream));
+    LSSP_HIP(hipMemsetAsync(li.U.d_coef, 0, sizeof(double) * line_coef_len(li.U), c->stream));
     // hand-off rows: one per level, NJ k entries and P j entries each
     const long tmax = std::max(li.L.tmax, li.U.tmax);
     return finish_line_tiles(c, li, tmax * NJ, tmax * P);
 }
+
+static int line_refill_sweep(lssp_amd_ctx *c, LineILU &li, int which, long n, const FactorView &f);
 
 int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const std::vector<int> &Lj,
                      const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
@@ -416,25 +339,10 @@ int build_line_sweep(lssp_amd_ctx *c, int n, const std::vector<int> &Lp, const s
     if (!line_enabled()) return LSSP_AMD_EUNSUPPORTED;
     LineGeom g;
     if (!detect_grid(n, Lp, Lj, Lx, Up, Uj, g)) return build_linefill(c, n, Lp, Lj, Lx, Up, Uj, Ux, li);
-    if (lineg_route(g)) {
-        const long plane = (long)g.nx * g.ny;
-        const int ncl = g.unitL ? 2 : 3;
-        CoefSrc sl, su;
-        sl.build(Lp, Lj, Lx, false, n, g.nx, plane, g.unitL ? 3 : 4);
-        su.build(Up, Uj, Ux, true, n, g.nx, plane, 4);
-        // k_lineg's components: S, W (, diag) = CoefSrc's 1, 2 (, 3)
-        std::vector<double> cl((size_t)n * ncl), cu((size_t)n * 3);
-        for (long r = 0; r < n; r++) {
-            for (int k = 0; k < ncl; k++) cl[r * ncl + k] = sl.get(r, 1 + k);
-            for (int k = 0; k < 3; k++) cu[r * 3 + k] = su.get(r, 1 + k);
-        }
-        return build_lineg(c, g, 0, ncl, cl, cu, li);
-    }
-    const long plane = (long)g.nx * g.ny;
-    CoefSrc cl, cu;
-    cl.build(Lp, Lj, Lx, false, n, g.nx, plane, g.unitL ? 3 : 4);
-    cu.build(Up, Uj, Ux, true, n, g.nx, plane, 4);
-    return build_line_tiles(c, g, &cl, &cu, li);
+    const FactorView L{Lp.data(), Lj.data(), Lx.data(), nullptr, false}, U{Up.data(), Uj.data(), Ux.data(), nullptr, false};
+    if (lineg_route(g)) return build_lineg(c, g, 0, g.unitL ? 2 : 3, L, U, li);
+    LSSP_TRY(build_line_tiles(c, g, li));
+    return line_refill_host(c, li, n, Lp, Lj, Lx, Up, Uj, Ux, line_refill_sweep);
 }
 
 // lssp_amd_ilu_create_dev: the ILU(0) of a complete nx x ny x nz box (unit L,
@@ -461,7 +369,7 @@ int build_line_sweep_box(lssp_amd_ctx *c, int nx, int ny, int nz, LineILU &li)
 {
     LineGeom g;
     if (!line_box_tiled(nx, ny, nz) || !box_geom(nx, ny, nz, g)) return LSSP_AMD_EUNSUPPORTED;
-    return build_line_tiles(c, g, nullptr, nullptr, li);
+    return build_line_tiles(c, g, li);
 }
 
 int line_rearm(lssp_amd_ctx *c, LineILU &li)
@@ -471,74 +379,39 @@ int line_rearm(lssp_amd_ctx *c, LineILU &li)
 }
 
 // ---------------------------------------------------------------------------
-// lssp_amd_ilu_refactor: CoefSrc::build + upload_sweep on the device
+// the coefficient streams of the k_line2 sweeps, from factors in HBM
 // ---------------------------------------------------------------------------
 // One thread per stream slot.  Tile blockIdx.x; blockIdx.y takes a contiguous
-// range of the tile's steps, in chunks of two steps (P * nj <= 128 slots each,
-// laid out back to back as upload_sweep does: slot = step * P * nj + p * nj + l).
-// A slot valid at its step (row i = s - l - p - sigma(p) on the line) reads its
-// row of the factored matrix F (pattern Fp / Fj: the grid neighbours,
-// ascending) and takes the entries on its sweep's side of the diagonal by
-// their offset -- plane: component 0, nx: 1, 1: 2 -- and, NA == 4, the pivot
-// (U) or the unit diagonal (L); a missing neighbour and every slot not valid at
-// its step are +0.0.  The U sweep's tiles are in mirrored coordinates: sweep
-// row r_s is natural row n-1 - r_s.  A thread keeps its (p, l) over the chunks,
-// so consecutive chunks read rows i, i + 2, ... of one line (the same cache
-// lines of F while they are warm); the chunk's NA doubles per slot go through
-// LDS and leave as one run of consecutive doubles, 64 per wave store.  Every
-// slot of every tile is written, so nothing of the previous values survives.
+// range of the tile's levels, in chunks of two levels (P * nj <= 128 slots each,
+// back to back: slot = level * P * nj + p * nj + l).  A slot that holds a row
+// (line_slot_row) gets that row's coefficients from the sweep's factor view
+// (line_coef_row); every other slot is +0.0.  The U sweep's tiles are in
+// mirrored coordinates: sweep row r_s is natural row n-1 - r_s.  A thread keeps
+// its (p, l) over the chunks, so consecutive chunks read rows i, i + 2, ... of
+// one line (the same cache lines of the factor while they are warm); the
+// chunk's NA doubles per slot go through LDS and leave as one run of
+// consecutive doubles, 64 per wave store.  Every slot of every tile is
+// written, so nothing of the previous values survives.
 template <int NA>
 __global__ __launch_bounds__(256) void k_coef_refill(const LineTile *__restrict__ tiles, int nx, int ny, long n,
-                                                     long plane, int P, int LV, int upper,
-                                                     const int *__restrict__ Fp, const int *__restrict__ Fj,
-                                                     const double *__restrict__ Fx, double *__restrict__ coef)
+                                                     long plane, int P, int LV, int upper, FactorView f,
+                                                     double *__restrict__ coef)
 {
     __shared__ double buf[256 * NA];
     const LineTile t = tiles[blockIdx.x];
     const int tid = threadIdx.x;
-    const int blk = P * t.nj;            // slots per step (<= 256: launch_line_refill)
-    const int spc = blk <= 128 ? 2 : 1;  // steps per chunk
+    const int blk = P * t.nj;            // slots per level (<= 256: line_refill_sweep)
+    const int spc = blk <= 128 ? 2 : 1;  // levels per chunk
     const int so = tid >= blk ? 1 : 0, rem = tid - so * blk, p = rem / t.nj, l = rem - p * t.nj;
-    const int sg = LV >= 2 ? (LV - 1) * (p / 4) : 0;  // line_sigma
-    const bool mine = tid < spc * blk && p < t.np;    // a plane of the tile (else +0.0 at every step)
-    const long line0 = mine ? ((long)(t.k0 + p) * ny + (t.j0 + l)) * nx : 0;
     const int nchunk = (t.T + spc - 1) / spc, per = (nchunk + (int)gridDim.y - 1) / (int)gridDim.y;
     const int c0 = blockIdx.y * per, c1 = min(nchunk, c0 + per);
     for (int ch = c0; ch < c1; ch++) {
         const int nslot = min(spc, t.T - ch * spc) * blk;
-        const int i = ch * spc + so - l - p - sg;
-        double ck = 0., cj = 0., ci = 0., cd = 0.;
-        if (mine && tid < nslot && i >= 0 && i < nx) {  // step_range
-            const long r = upper ? n - 1 - (line0 + i) : line0 + i;
-            const int b = Fp[r], e = Fp[r + 1];
-            // a grid row holds at most 7 entries: all loads issued before the first is used
-            int fj[7];
-            double fx[7];
-#pragma unroll
-            for (int u = 0; u < 7; u++) {
-                const bool in = b + u < e;
-                fj[u] = in ? Fj[b + u] : (int)r;
-                fx[u] = in ? Fx[b + u] : 0.;
-            }
-#pragma unroll
-            for (int u = 0; u < 7; u++) {
-                const long off = upper ? (long)fj[u] - r : r - (long)fj[u];
-                if (b + u >= e) continue;
-                if (off > 0) {
-                    if (off == plane) ck = fx[u];
-                    else if (off == nx) cj = fx[u];
-                    else ci = fx[u];
-                } else if (off == 0) {
-                    cd = upper ? fx[u] : 1.;
-                }
-            }
-        }
-        if (tid < nslot) {
-            buf[tid * NA] = ck;
-            buf[tid * NA + 1] = cj;
-            buf[tid * NA + 2] = ci;
-            if (NA == 4) buf[tid * NA + 3] = cd;
-        }
+        const long rs = tid < nslot ? line_slot_row(ch * spc + so, p, l, t.j0, t.k0, t.np, nx, ny, LV) : -1;
+        double cf[4] = {0., 0., 0., 0.};
+        if (rs >= 0) line_coef_row(rs, upper != 0, n, nx, plane, NA, f, cf);
+        if (tid < nslot)
+            for (int a = 0; a < NA; a++) buf[tid * NA + a] = cf[a];
         __syncthreads();
         double *o = coef + (t.cbase + (long)ch * spc * blk) * NA;
         for (int e = tid; e < nslot * NA; e += 256) o[e] = buf[e];
@@ -546,23 +419,52 @@ __global__ __launch_bounds__(256) void k_coef_refill(const LineTile *__restrict_
     }
 }
 
-int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const int *Fp, const int *Fj, const double *Fx)
+// one sweep's stream (which: 0 L, 1 U) from its factor view
+static int line_refill_sweep(lssp_amd_ctx *c, LineILU &li, int which, long n, const FactorView &f)
 {
+    LineSweep &ls = which ? li.U : li.L;
     const long plane = (long)li.g.nx * li.g.ny;
-    if (li.P * li.NJ > 256) return LSSP_AMD_EUNSUPPORTED;  // k_coef_refill: a step's slots within one workgroup
-    for (int upper = 0; upper < 2; upper++) {
-        LineSweep &ls = upper ? li.U : li.L;
-        if (ls.ntiles <= 0) continue;
-        const dim3 grid((unsigned)ls.ntiles, 8);
-        if (ls.NA == 4)
-            k_coef_refill<4><<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.nx, ls.ny, n, plane, ls.P, ls.LV, upper, Fp,
-                                                          Fj, Fx, ls.d_coef);
-        else
-            k_coef_refill<3><<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.nx, ls.ny, n, plane, ls.P, ls.LV, upper, Fp,
-                                                          Fj, Fx, ls.d_coef);
-    }
-    LSSP_HIP(hipGetLastError());
+    if (li.P * li.NJ > 256) return LSSP_AMD_EUNSUPPORTED;  // k_coef_refill: a level's slots within one workgroup
     li.lstream_of = nullptr;
+    if (ls.ntiles <= 0) return LSSP_AMD_OK;
+    const dim3 grid((unsigned)ls.ntiles, 8);
+    if (ls.NA == 4)
+        k_coef_refill<4><<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.nx, ls.ny, n, plane, ls.P, ls.LV, which, f, ls.d_coef);
+    else
+        k_coef_refill<3><<<grid, 256, 0, c->stream>>>(ls.d_tiles, ls.nx, ls.ny, n, plane, ls.P, ls.LV, which, f, ls.d_coef);
+    LSSP_HIP(hipGetLastError());
+    return LSSP_AMD_OK;
+}
+
+int launch_line_refill(lssp_amd_ctx *c, LineILU &li, long n, const FactorView &fl, const FactorView &fu)
+{
+    LSSP_TRY(line_refill_sweep(c, li, 0, n, fl));
+    return line_refill_sweep(c, li, 1, n, fu);
+}
+
+// A host create's coefficient streams (either kind): each host factor in turn
+// goes to temporary device buffers -- the transient is one factor's CSR, about
+// 12 B per entry -- and through its sweep's refill.  No RefactorPlan is made.
+int line_refill_host(lssp_amd_ctx *c, LineILU &li, long n, const std::vector<int> &Lp, const std::vector<int> &Lj,
+                     const std::vector<double> &Lx, const std::vector<int> &Up, const std::vector<int> &Uj,
+                     const std::vector<double> &Ux, LineSweepRefill refill)
+{
+    for (int which = 0; which < 2; which++) {
+        const std::vector<int> &Tp = which ? Up : Lp, &Tj = which ? Uj : Lj;
+        const std::vector<double> &Tx = which ? Ux : Lx;
+        const size_t nnz = (size_t)Tp[n];
+        DevBufs tmp;
+        int *dp, *dj;
+        double *dx;
+        LSSP_HIP(tmp.get(&dp, (size_t)n + 1));
+        LSSP_HIP(tmp.get(&dj, nnz));
+        LSSP_HIP(tmp.get(&dx, nnz));
+        LSSP_HIP(hipMemcpyAsync(dp, Tp.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
+        LSSP_HIP(hipMemcpyAsync(dj, Tj.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, c->stream));
+        LSSP_HIP(hipMemcpyAsync(dx, Tx.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, c->stream));
+        LSSP_TRY(refill(c, li, which, n, FactorView{dp, dj, dx, nullptr, false}));
+        LSSP_HIP(hipStreamSynchronize(c->stream));  // before the temporaries go
+    }
     return LSSP_AMD_OK;
 }
 

@@ -1,10 +1,11 @@
 // iluk_refill_check.cpp -- the index arithmetic of lssp_amd_iluk_refactor's
 // kernels on the host (no GPU, no HIP): the per-row bodies of k_iluk_match,
 // k_iluk_scatter, k_pk6_refill_scalar and k_linef_refill
-// (lssp_amd/csrc/iluk_refactor_dev.h) run against independent restatements of
-// the pattern rule, of build_packets6's value placement and of FillCoef::build +
-// fill_upload, on exactly-sized heap arrays, so a sanitizer sees any access
-// outside them:
+// (lssp_amd/csrc/iluk_refactor_dev.h), and the row rules and slot inversions of
+// both line sweeps' coefficient streams (k_coef_refill, k_linef_refill,
+// build_lineg), run against independent restatements of the pattern rule, of
+// build_packets6's value placement and of the stream layouts, on exactly-sized
+// heap arrays, so a sanitizer sees any access outside them:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -Ilssp_amd/csrc tools/iluk_refill_check.cpp -o /tmp/iluk_refill_check && /tmp/iluk_refill_check
 // Exit status 0 and "ok" when every case matches.
@@ -205,13 +206,180 @@ static void check_packets(std::mt19937 &g, const Factor &F, bool upper, int *ep_
     }
 }
 
-// ---- k_linef: the ILU(1) pattern of a box, build_linefill's tiles, fill_upload's placement ----
+// ---- the line sweeps' coefficient streams (k_coef_refill, k_linef_refill, build_lineg) ----
+// The shared row rules and slot inversions against a restatement that shares
+// nothing with them: a row's coefficients are looked up by NEIGHBOUR COLUMN (not
+// classified by offset), and the rows are placed FORWARD, tile by tile, from
+// (plane, line, i) to their slot (not inverted from the slot); everything not
+// placed is +0.0.  Inputs: a lone L (strict part, a non-unit diagonal last), a
+// lone U (pivot first) and the combined F with and without diagonal positions.
 struct Tile {
     int j0, nj, k0, np, T;
     long cbase;
 };
 
-static std::vector<int> widths(int m)  // fill_widths
+struct GridFactors {
+    long n = 0;
+    std::vector<int> Lp{0}, Lj, Up{0}, Uj, Fp{0}, Fj, dpos;
+    std::vector<double> Lx, Ux, Fx;
+    std::vector<std::map<long, double>> lrow, urow;  // per row: column -> value (diagonals included)
+};
+
+// lower(r) / upper(r): the strict neighbour columns of row r, ascending
+template <class LO, class UP>
+static GridFactors grid_factors(std::mt19937 &g, long n, LO lower, UP upper)
+{
+    std::uniform_real_distribution<double> u(-1, 1), d(0.5, 1.5);
+    GridFactors G;
+    G.n = n;
+    G.lrow.resize(n);
+    G.urow.resize(n);
+    for (long r = 0; r < n; r++) {
+        const double ldiag = d(g), piv = d(g);  // L's diagonal is NOT 1.0
+        for (long c : lower(r)) {
+            const double v = u(g);
+            G.Lj.push_back((int)c), G.Lx.push_back(v), G.Fj.push_back((int)c), G.Fx.push_back(v);
+            G.lrow[r][c] = v;
+        }
+        G.Lj.push_back((int)r), G.Lx.push_back(ldiag);
+        G.lrow[r][r] = ldiag;
+        G.dpos.push_back((int)G.Fj.size());
+        G.Fj.push_back((int)r), G.Fx.push_back(piv);
+        G.Uj.push_back((int)r), G.Ux.push_back(piv);
+        G.urow[r][r] = piv;
+        for (long c : upper(r)) {
+            const double v = u(g);
+            G.Uj.push_back((int)c), G.Ux.push_back(v), G.Fj.push_back((int)c), G.Fx.push_back(v);
+            G.urow[r][c] = v;
+        }
+        G.Lp.push_back((int)G.Lj.size()), G.Up.push_back((int)G.Uj.size()), G.Fp.push_back((int)G.Fj.size());
+    }
+    for (auto *v : {&G.Lp, &G.Lj, &G.Up, &G.Uj, &G.Fp, &G.Fj, &G.dpos}) v->shrink_to_fit();
+    for (auto *v : {&G.Lx, &G.Ux, &G.Fx}) v->shrink_to_fit();
+    return G;
+}
+
+// the coefficients of natural row r on one sweep: the neighbours at the given
+// distances, in component order, then (NA > noff) the diagonal
+static void want_row(const GridFactors &G, long r, bool upper, const std::vector<long> &dist, int NA, bool unit,
+                     double *out)
+{
+    const std::map<long, double> &row = upper ? G.urow[r] : G.lrow[r];
+    for (size_t a = 0; a < dist.size(); a++) {
+        const auto it = row.find(upper ? r + dist[a] : r - dist[a]);
+        out[a] = it == row.end() ? 0.0 : it->second;
+    }
+    if (NA > (int)dist.size()) out[dist.size()] = !upper && unit ? 1.0 : row.at(r);
+}
+
+// the three inputs of a sweep: 0 the lone factor (stored diagonal), 1 F without
+// diagonal positions, 2 F with them (both: L's diagonal the unit)
+static FactorView view_of(const GridFactors &G, bool upper, int input)
+{
+    if (input == 0)
+        return upper ? FactorView{G.Up.data(), G.Uj.data(), G.Ux.data(), nullptr, false}
+                     : FactorView{G.Lp.data(), G.Lj.data(), G.Lx.data(), nullptr, false};
+    return FactorView{G.Fp.data(), G.Fj.data(), G.Fx.data(), input == 2 ? G.dpos.data() : nullptr, true};
+}
+
+static long lay_out(std::vector<Tile> &tiles)
+{
+    long rows_total = 0;
+    for (Tile &t : tiles) {
+        t.cbase = rows_total;
+        rows_total += (long)t.T * 8 * t.nj;
+    }
+    return rows_total;
+}
+
+// k_line2: the 5-/7-point ILU(0) of a box whose plane k is cut from plane k-1
+// where cut[k]; 16 x 8 tiles between the cuts, the U tiles mirrored
+static void check_line0(std::mt19937 &g, int nx, int ny, int nz, const std::vector<int> &cutk)
+{
+    const long pl = (long)nx * ny, n = pl * nz;
+    std::vector<char> kin(nz, 1);
+    kin[0] = 0;
+    for (int k : cutk) kin[k] = 0;
+    const GridFactors G = grid_factors(
+        g, n,
+        [&](long r) {
+            const int i = (int)(r % nx), j = (int)((r / nx) % ny), k = (int)(r / pl);
+            std::vector<long> c;
+            if (k > 0 && kin[k]) c.push_back(r - pl);
+            if (j > 0) c.push_back(r - nx);
+            if (i > 0) c.push_back(r - 1);
+            return c;
+        },
+        [&](long r) {
+            const int i = (int)(r % nx), j = (int)((r / nx) % ny), k = (int)(r / pl);
+            std::vector<long> c;
+            if (i < nx - 1) c.push_back(r + 1);
+            if (j < ny - 1) c.push_back(r + nx);
+            if (k < nz - 1 && kin[k + 1]) c.push_back(r + pl);
+            return c;
+        });
+    std::vector<std::pair<int, int>> kt;  // plane segments between the cuts, in tiles of <= 8 planes
+    for (int k = 0; k < nz;) {
+        int e = k + 1;
+        while (e < nz && kin[e]) e++;
+        for (int k0 = k; k0 < e; k0 += 8) kt.push_back({k0, std::min(8, e - k0)});
+        k = e;
+    }
+    const int S = (int)kt.size(), W = (ny + 15) / 16;
+    auto sig = [](int p) { return p >= 4 ? 1 : 0; };  // LV = 2: wave 1's planes run one level later
+    for (int upper = 0; upper < 2; upper++)
+        for (int input = 0; input < 3; input++)
+            for (int NA = upper ? 4 : 3; NA <= 4; NA++) {
+                std::vector<Tile> tiles((size_t)S * W);
+                for (int K = 0; K < S; K++)
+                    for (int J = 0, j0 = 0; J < W; J++) {
+                        Tile t;
+                        t.j0 = j0;
+                        t.nj = ny / W + (J < ny % W ? 1 : 0);
+                        j0 += t.nj;
+                        t.k0 = kt[K].first;
+                        t.np = kt[K].second;
+                        t.T = (nx + t.nj + t.np - 2 + sig(t.np - 1) + 1) / 2 * 2;
+                        if (!upper) tiles[(size_t)K * W + J] = t;
+                        else {
+                            t.j0 = ny - t.j0 - t.nj;
+                            t.k0 = nz - t.k0 - t.np;
+                            tiles[(size_t)(S - 1 - K) * W + (W - 1 - J)] = t;
+                        }
+                    }
+                const long rows_total = lay_out(tiles);
+                std::vector<double> want((size_t)rows_total * NA, 0.0), got((size_t)rows_total * NA, -3.0);
+                long placed = 0;
+                for (const Tile &t : tiles)
+                    for (int p = 0; p < t.np; p++)
+                        for (int l = 0; l < t.nj; l++)
+                            for (int i = 0; i < nx; i++) {
+                                const long v = i + l + p + sig(p);
+                                const long rs = ((long)(t.k0 + p) * ny + (t.j0 + l)) * nx + i;
+                                CHECK(v < t.T, "line0: a row past its tile's levels");
+                                want_row(G, upper ? n - 1 - rs : rs, upper != 0, {pl, nx, 1}, NA, input != 0,
+                                         want.data() + (size_t)(t.cbase + v * 8 * t.nj + p * t.nj + l) * NA);
+                                placed++;
+                            }
+                CHECK(placed == n, "line0: the tiles place %ld of %ld rows (%d x %d x %d)", placed, n, nx, ny, nz);
+                const FactorView f = view_of(G, upper != 0, input);
+                for (const Tile &t : tiles)
+                    for (int s = 0; s < t.T; s++)
+                        for (int p = 0; p < 8; p++)
+                            for (int l = 0; l < t.nj; l++) {
+                                double *dst = got.data() + (size_t)(t.cbase + (long)s * 8 * t.nj + p * t.nj + l) * NA;
+                                const long rs = line_slot_row(s, p, l, t.j0, t.k0, t.np, nx, ny, 2);
+                                CHECK(rs < n, "line0: a slot's row past the grid");
+                                if (rs >= 0 && rs < n) line_coef_row(rs, upper != 0, n, nx, pl, NA, f, dst);
+                                else
+                                    for (int a = 0; a < NA; a++) dst[a] = 0.0;
+                            }
+                CHECK(!memcmp(want.data(), got.data(), sizeof(double) * want.size()),
+                      "line0: stream differs (%d x %d x %d upper %d input %d NA %d)", nx, ny, nz, upper, input, NA);
+            }
+}
+
+static std::vector<int> widths(int m)  // mirror-symmetric widths <= 16 of the skewed columns
 {
     for (int W = (m + 15) / 16;; W++) {
         const int base = m / W, extra = m % W;
@@ -223,109 +391,92 @@ static std::vector<int> widths(int m)  // fill_widths
     }
 }
 
+// k_linef: the ILU(1) pattern of a 7-point box; S x W tiles of the skewed
+// columns j' = j + k, the U tiles mirrored
 static void check_linef(std::mt19937 &g, int nx, int ny, int nz)
 {
     const long pl = (long)nx * ny, n = pl * nz;
-    std::uniform_real_distribution<double> u(-1, 1);
-    // F: row r = the ILU(1) pattern of the 7-point box (detect_fill1), sorted
-    Factor F;
-    F.n = (int)n;
-    F.Fp.push_back(0);
-    for (long r = 0; r < n; r++) {
-        const int i = (int)(r % nx), j = (int)((r / nx) % ny), k = (int)(r / pl);
-        std::vector<long> c;
-        if (k > 0) c.push_back(r - pl);
-        if (k > 0 && i < nx - 1) c.push_back(r - pl + 1);
-        if (k > 0 && j < ny - 1) c.push_back(r - pl + nx);
-        if (j > 0) c.push_back(r - nx);
-        if (j > 0 && i < nx - 1) c.push_back(r - nx + 1);
-        if (i > 0) c.push_back(r - 1);
-        F.dpos.push_back((int)(F.Fj.size() + c.size()));
-        c.push_back(r);
-        if (i < nx - 1) c.push_back(r + 1);
-        if (j < ny - 1 && i > 0) c.push_back(r + nx - 1);
-        if (j < ny - 1) c.push_back(r + nx);
-        if (k < nz - 1 && j > 0) c.push_back(r + pl - nx);
-        if (k < nz - 1 && i > 0) c.push_back(r + pl - 1);
-        if (k < nz - 1) c.push_back(r + pl);
-        for (long q : c) F.Fj.push_back((int)q);
-        F.Fp.push_back((int)F.Fj.size());
-    }
-    std::vector<double> Fx(F.Fj.size());
-    for (double &v : Fx) v = u(g);
-    // tiles (build_linefill): S x W of the skewed columns j' = j + k, the U tile mirrored
+    const GridFactors G = grid_factors(
+        g, n,
+        [&](long r) {
+            const int i = (int)(r % nx), j = (int)((r / nx) % ny), k = (int)(r / pl);
+            std::vector<long> c;
+            if (k > 0) c.push_back(r - pl);
+            if (k > 0 && i < nx - 1) c.push_back(r - pl + 1);
+            if (k > 0 && j < ny - 1) c.push_back(r - pl + nx);
+            if (j > 0) c.push_back(r - nx);
+            if (j > 0 && i < nx - 1) c.push_back(r - nx + 1);
+            if (i > 0) c.push_back(r - 1);
+            return c;
+        },
+        [&](long r) {
+            const int i = (int)(r % nx), j = (int)((r / nx) % ny), k = (int)(r / pl);
+            std::vector<long> c;
+            if (i < nx - 1) c.push_back(r + 1);
+            if (j < ny - 1 && i > 0) c.push_back(r + nx - 1);
+            if (j < ny - 1) c.push_back(r + nx);
+            if (k < nz - 1 && j > 0) c.push_back(r + pl - nx);
+            if (k < nz - 1 && i > 0) c.push_back(r + pl - 1);
+            if (k < nz - 1) c.push_back(r + pl);
+            return c;
+        });
     const int m = ny + nz - 1;
     const std::vector<int> wd = widths(m);
     const int W = (int)wd.size(), S = (nz + 7) / 8;
     std::vector<int> js(W + 1, 0);
     for (int J = 0; J < W; J++) js[J + 1] = js[J] + wd[J];
-    for (int upper = 0; upper < 2; upper++) {
-        const int NA = upper ? 7 : 6 + (int)(g() % 2);
-        std::vector<Tile> tiles((size_t)S * W);
-        for (int K = 0; K < S; K++)
-            for (int J = 0; J < W; J++) {
-                Tile t;
-                t.j0 = js[J];
-                t.nj = wd[J];
-                t.k0 = K * 8;
-                t.np = std::min(8, nz - t.k0);
-                const int T = nx + 2 * (t.nj - 1) + (t.np - 1) + ((t.np - 1) >> 2) + 1;
-                t.T = (T + 1) / 2 * 2;
-                if (!upper) tiles[(size_t)K * W + J] = t;
-                else {
-                    t.j0 = m - t.j0 - t.nj;
-                    t.k0 = nz - t.k0 - t.np;
-                    tiles[(size_t)(S - 1 - K) * W + (W - 1 - J)] = t;
+    for (int upper = 0; upper < 2; upper++)
+        for (int input = 0; input < 3; input++)
+            for (int NA = upper ? 7 : 6; NA <= 7; NA++) {
+                std::vector<Tile> tiles((size_t)S * W);
+                for (int K = 0; K < S; K++)
+                    for (int J = 0; J < W; J++) {
+                        Tile t;
+                        t.j0 = js[J];
+                        t.nj = wd[J];
+                        t.k0 = K * 8;
+                        t.np = std::min(8, nz - t.k0);
+                        const int T = nx + 2 * (t.nj - 1) + (t.np - 1) + ((t.np - 1) >> 2) + 1;
+                        t.T = (T + 1) / 2 * 2;
+                        if (!upper) tiles[(size_t)K * W + J] = t;
+                        else {
+                            t.j0 = m - t.j0 - t.nj;
+                            t.k0 = nz - t.k0 - t.np;
+                            tiles[(size_t)(S - 1 - K) * W + (W - 1 - J)] = t;
+                        }
+                    }
+                const long rows_total = lay_out(tiles);
+                std::vector<double> want((size_t)rows_total * NA, 0.0), got((size_t)rows_total * NA, -3.0);
+                long placed = 0;
+                for (const Tile &t : tiles) {
+                    for (int p = 0; p < t.np; p++)
+                        for (int l = 0; l < t.nj; l++) {
+                            const int j = t.j0 + l - (t.k0 + p);
+                            if (j < 0 || j >= ny) continue;
+                            for (int i = 0; i < nx; i++) {
+                                const long v = i + 2 * l + p + (p >> 2);
+                                const long rs = ((long)(t.k0 + p) * ny + j) * nx + i;
+                                want_row(G, upper ? n - 1 - rs : rs, upper != 0, {pl, pl - 1, pl - nx, nx, nx - 1, 1}, NA,
+                                         input != 0, want.data() + (size_t)(t.cbase + v * 8 * t.nj + p * t.nj + l) * NA);
+                                placed++;
+                            }
+                        }
                 }
-            }
-        long rows_total = 0;
-        for (Tile &t : tiles) {
-            t.cbase = rows_total;
-            rows_total += (long)t.T * 8 * t.nj;
-        }
-        // want: FillCoef::build, then fill_upload's forward placement, the rest +0.0
-        std::vector<double> src((size_t)n * NA, 0.0);
-        for (long r = 0; r < n; r++) {
-            double *row = src.data() + (size_t)(upper ? n - 1 - r : r) * NA;
-            const int d = F.dpos[r];
-            if (NA == 7) row[6] = upper ? Fx[d] : 1.0;
-            for (int q = upper ? d + 1 : F.Fp[r]; q < (upper ? F.Fp[r + 1] : d); q++) {
-                const long off = upper ? F.Fj[q] - r : r - F.Fj[q];
-                const int a = off == pl ? 0 : off == pl - 1 ? 1 : off == pl - nx ? 2 : off == nx ? 3 : off == nx - 1 ? 4 : 5;
-                row[a] = Fx[q];
-            }
-        }
-        std::vector<double> want((size_t)rows_total * NA, 0.0), got((size_t)rows_total * NA, -3.0);
-        long placed = 0;
-        for (const Tile &t : tiles)
-            for (int p = 0; p < t.np; p++)
-                for (int l = 0; l < t.nj; l++) {
-                    const int j = t.j0 + l - (t.k0 + p);
-                    if (j < 0 || j >= ny) continue;
-                    for (int i = 0; i < nx; i++) {
-                        const long v = i + 2 * l + p + (p >> 2);
-                        const long r = ((long)(t.k0 + p) * ny + j) * nx + i;
-                        double *dst = want.data() + (size_t)(t.cbase + v * 8 * t.nj + p * t.nj + l) * NA;
-                        for (int a = 0; a < NA; a++) dst[a] = src[(size_t)r * NA + a];
-                        placed++;
+                CHECK(placed == n, "linef: the tiles place %ld of %ld rows (%d x %d x %d)", placed, n, nx, ny, nz);
+                const FactorView f = view_of(G, upper != 0, input);
+                for (const Tile &t : tiles) {
+                    const long slots = (long)t.T * 8 * t.nj;
+                    for (long s = 0; s < slots; s++) {
+                        double *dst = got.data() + (size_t)(t.cbase + s) * NA;
+                        const long rs = linef_slot_row(s, t.j0, t.nj, t.k0, t.np, nx, ny);
+                        if (rs >= 0 && rs < n) linef_coef_row(rs, upper != 0, n, nx, pl, NA, f, dst);
+                        else
+                            for (int a = 0; a < NA; a++) dst[a] = 0.0;
                     }
                 }
-        CHECK(placed == n, "linef: the tiles place %ld of %ld rows (%d x %d x %d)", placed, n, nx, ny, nz);
-        // got: k_linef_refill's body, every slot of every tile
-        for (const Tile &t : tiles) {
-            const long slots = (long)t.T * 8 * t.nj;
-            for (long s = 0; s < slots; s++) {
-                double *dst = got.data() + (size_t)(t.cbase + s) * NA;
-                const long rs = linef_slot_row(s, t.j0, t.nj, t.k0, t.np, nx, ny);
-                if (rs >= 0 && rs < n)
-                    linef_coef_row(rs, upper != 0, n, nx, pl, NA, F.Fp.data(), F.Fj.data(), F.dpos.data(), Fx.data(), dst);
-                else
-                    for (int a = 0; a < NA; a++) dst[a] = 0.0;
+                CHECK(!memcmp(want.data(), got.data(), sizeof(double) * want.size()),
+                      "linef: stream differs (%d x %d x %d upper %d input %d NA %d)", nx, ny, nz, upper, input, NA);
             }
-        }
-        CHECK(!memcmp(want.data(), got.data(), sizeof(double) * want.size()),
-              "linef: stream differs (%d x %d x %d upper %d NA %d)", nx, ny, nz, upper, NA);
-    }
 }
 
 int main()
@@ -344,12 +495,20 @@ int main()
         cases++;
     }
     for (int ep : {4, 8, 16, 24}) CHECK(ep_seen[ep] > 0, "no packet case of EP %d", ep);
-    // one tile; ragged j tiles, 8 + 5 planes; tiles off the grid; 2 planes; a single plane column
-    const int boxes[][3] = {{4, 3, 2}, {9, 21, 13}, {5, 7, 20}, {13, 37, 11}, {3, 3, 9}, {6, 40, 2}};
+    // one tile; ragged j tiles, 8 + 5 planes; tiles off the grid; 2 planes; a single plane column; 2-D
+    const int boxes[][3] = {{4, 3, 2}, {9, 21, 13}, {5, 7, 20}, {13, 37, 11}, {3, 3, 9}, {6, 40, 2}, {6, 10, 1}};
     for (const auto &b : boxes) {
         check_linef(g, b[0], b[1], b[2]);
         cases++;
     }
+    // k_line2: 9 + 8 lines and 8 + 1 planes; fewer than 8 planes and ragged lines; cuts (a one-plane
+    // segment, a segment longer than a tile); 2-D
+    check_line0(g, 2, 17, 9, {});
+    check_line0(g, 5, 21, 5, {});
+    check_line0(g, 4, 9, 12, {1, 2});
+    check_line0(g, 3, 33, 20, {5, 16});
+    check_line0(g, 6, 10, 1, {});
+    cases += 5;
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
