@@ -341,6 +341,49 @@ int lssp_amd_comm_init_host(lssp_amd_ctx *ctx, int nranks, int rank, const lssp_
 int lssp_amd_mat_upload_dist(lssp_amd_ctx *ctx, int n_global, int row0, int nlocal,
                              const int *Ap, const int *Aj, const double *Ax, lssp_amd_mat **A);
 int lssp_amd_mat_local_rows(const lssp_amd_mat *A, int *row0, int *nlocal, int *nhalo);
+/* The same handle from DEVICE arrays: local rows [row0, row0 + nlocal) with
+ * GLOBAL column indices, dAp (nlocal + 1), dAj and dAx (nnz) in HBM.  Equal to
+ * lssp_amd_mat_upload_dist of the same arrays in every observable way
+ * (lssp_amd_mat_local_rows, _layout, _rowcodes, _valcodes (0), _bytes, _info,
+ * every product, every solve bitwise, the status for the same input); that call
+ * copies its arrays to HBM and runs this builder.  The handle owns copies: the
+ * caller may free its arrays on return.
+ * Collective, canonical partition only (rank r holds rows [r blk, r blk + blk),
+ * blk = ceil(n_global / P)).  dAp[0] == 0, dAp non-decreasing, dAp[nlocal] ==
+ * nnz and every column in [0, n_global) are checked on the device; the ranks
+ * agree on the outcome before anything indexes with a column and before every
+ * collective step, so one rank's bad input makes EVERY rank return
+ * LSSP_AMD_EINVAL (an allocation that fails on one: LSSP_AMD_ENOMEM on all),
+ * with nothing left allocated.  A NULL ctx or A returns LSSP_AMD_EINVAL at once.
+ * The halo list (flag, compact, sort, de-duplicate), the renumbering [owned |
+ * halo] and the halo-free chunk run are made on the device; the halo list, P
+ * counts, the send indices and two words per 256-row chunk cross to the host,
+ * never O(nnz) data.  Peak device memory above the finished handle: 8 B per row
+ * and 16 B per halo-column ENTRY (duplicates included) plus the radix sort's
+ * scratch of about as much again, freed on return.  On one rank (no
+ * communicator needed) there is no halo and no exchange. */
+int lssp_amd_mat_from_device_dist(lssp_amd_ctx *ctx, int n_global, int row0, int nlocal, int nnz,
+                                  const int *dAp, const int *dAj, const double *dAx, lssp_amd_mat **A);
+/* The rank's diagonal block of A as a single-rank nlocal x nlocal handle B: the
+ * entries of A whose column the rank owns, in A's entry order, made from A's
+ * resident arrays (per-row counts, a scan, a fill).  B is equal in every
+ * observable way to lssp_amd_mat_upload of the block cut out on the host, value
+ * codes included; for an A without halo columns it is a copy of A.  A row left
+ * without an entry stays empty (the create calls then refuse the missing
+ * diagonal).  B is what lssp_amd_pc_create_dev / _ilut_create_dev /
+ * _bilu_create_dev and, after a refresh, the refactor calls take for the rank's
+ * block-Jacobi ILU; lssp_amd_solve(A, M) takes the block-Jacobi path.  Local, no
+ * collective.  A NULL argument or a rank without rows: LSSP_AMD_EINVAL.  Peak
+ * device memory above B: one more copy of the block (12 B per entry + 8 B per
+ * row), freed on return. */
+int lssp_amd_mat_local_block(lssp_amd_ctx *ctx, const lssp_amd_mat *A, lssp_amd_mat **B);
+/* B's values again from the values A holds now (after
+ * lssp_amd_mat_update_values on A), finished as lssp_amd_mat_update_values
+ * finishes: the value codes rebuilt or dropped.  The device checks that A's
+ * owned entries per row are B's row lengths; a mismatch, a distributed B or
+ * another number of rows returns LSSP_AMD_EINVAL with B unchanged.  Local, no
+ * collective; 8 B per entry of B are held until it returns. */
+int lssp_amd_mat_local_block_refresh(lssp_amd_ctx *ctx, lssp_amd_mat *B, const lssp_amd_mat *A);
 
 /* ---- device index arrays: the int members of lssp_mat_csr / lssp_mat_coo /
  *      lssp_mat_bcsr (type-defs.h:15-55) in HBM, as lssp_amd_vec_* for doubles */
@@ -467,12 +510,15 @@ int lssp_amd_mat_from_device(lssp_amd_ctx *ctx, int nrows, int ncols, int nnz, c
  *      (column coding, window layout, level lists, tiles, stream layout,
  *      hand-off buffers) is kept, and nothing crosses the host. */
 /* dAx: DEVICE memory, nnz values in the entry order of the arrays the handle
- * was made from (lssp_amd_mat_upload or lssp_amd_mat_from_device).  Afterwards
+ * was made from (lssp_amd_mat_upload, lssp_amd_mat_from_device,
+ * lssp_amd_mat_upload_dist or lssp_amd_mat_from_device_dist).  Afterwards
  * every product and solve on A is bitwise that of a fresh handle made from the
  * same pattern with these values; lssp_amd_mat_layout / _bytes / _info answer
- * as before.  nnz other than the handle's or a NULL argument: LSSP_AMD_EINVAL;
- * a distributed matrix: LSSP_AMD_EUNSUPPORTED; A is unchanged in both cases.
- * Returns when the stream has finished. */
+ * as before.  nnz other than the handle's or a NULL argument: LSSP_AMD_EINVAL
+ * with A unchanged.  On a distributed matrix the call is local to the rank (its
+ * values are its own: no collective) and builds no value codes; its products
+ * are split at the halo rows, so coding them would take one more agreement
+ * round.  Returns when the stream has finished. */
 int lssp_amd_mat_update_values(lssp_amd_ctx *ctx, lssp_amd_mat *A, const double *dAx, int nnz);
 /* Factor M again from the values A holds now, keeping every schedule.
  * Afterwards lssp_amd_ilu_apply / _apply_async / _trisolve / lssp_amd_solve /
@@ -485,7 +531,8 @@ int lssp_amd_mat_update_values(lssp_amd_ctx *ctx, lssp_amd_mat *A, const double 
  * -- from_factors / from_ldu, ILUT, level >= 1, block-Jacobi, BILUK, the
  * one-workgroup sweeps of a small 2-D grid (*lines == ny), general packet-swept
  * factors -- and a distributed A return LSSP_AMD_EUNSUPPORTED with M unchanged
- * and usable.
+ * and usable.  For a rank's block-Jacobi factor take lssp_amd_mat_local_block
+ * first (and lssp_amd_mat_local_block_refresh before each refactor).
  * A must be n x n with exactly the factor's pattern (per row: L's strict part,
  * the diagonal, U's strict part), i.e. column-sorted rows that hold their
  * diagonal, as the matrix M was created from; compared on the device, a
@@ -514,7 +561,8 @@ int lssp_amd_ilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_mat
  * whose two sweeps run on packet schedules.  An ILUK / ILUT handle, a handle
  * from lssp_amd_ilu_from_ldu / _from_factors, bs 9..32, a handle on the
  * sync-free fallback (a factor row longer than 24 entries) and a distributed A
- * return LSSP_AMD_EUNSUPPORTED with M unchanged and usable.
+ * return LSSP_AMD_EUNSUPPORTED with M unchanged and usable.  For a rank's
+ * diagonal block take lssp_amd_mat_local_block first.
  * Pattern rule: A is n x n with M's n and has the BLOCK graph M was created
  * from -- every entry of A lies in a block the creating matrix had, and every
  * block the creating matrix had holds at least one entry of A.  The symbolic
@@ -559,7 +607,8 @@ int lssp_amd_bilu_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_ma
  * single-sweep arrays were built while every pivot was exactly 1.0 (its U
  * sweeps never read the pivots), a handle whose creating matrix repeated a
  * column in a row, and a distributed A return LSSP_AMD_EUNSUPPORTED with M
- * unchanged and usable.
+ * unchanged and usable.  For a rank's diagonal block take
+ * lssp_amd_mat_local_block first.
  * Pattern rule, checked on the device with nothing of A trusted: A is n x n
  * with M's n, every row's columns are strictly ascending and inside [0, n), and
  * A's pattern is exactly that of the creating matrix after its column sort (a
@@ -600,7 +649,7 @@ int lssp_amd_iluk_refactor(lssp_amd_ctx *ctx, lssp_amd_ilu *M, const lssp_amd_ma
  * Jacobi, an unsorted row, a missing diagonal or neighbour, a matrix that is
  * no such box, a small 2-D grid on the one-workgroup sweeps
  * (lssp_amd_ilu_sweep_layout *lines == ny there), LSSP_AMD_LINE=0, a distributed
- * A; use lssp_amd_ilu_create for those -- or lssp_amd_iluk_create_dev (below),
+ * A (take its lssp_amd_mat_local_block first); use lssp_amd_ilu_create for those -- or lssp_amd_iluk_create_dev (below),
  * which also makes the level-1 handle on the device.  NULL arguments, a kind
  * that is neither ILUK nor ILUT, or nrows != ncols: LSSP_AMD_EINVAL.  A HIP
  * error part-way: LSSP_AMD_EHIP, everything freed.  Returns when the stream has
@@ -631,9 +680,9 @@ int lssp_amd_ilu_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, 
  * LSSP_AMD_EUNSUPPORTED with *out == NULL, nothing allocated, A and ctx
  * untouched: ILUT, level >= 2, block-Jacobi, nx == 2 (or ny == 2), a small 2-D
  * grid on the one-workgroup sweeps (*lines == ny; LSSP_AMD_LINEG=0 keeps the
- * tiles), LSSP_AMD_LINE=0, a distributed A, an unsorted row, a missing diagonal
- * or neighbour, any matrix that is no such box; use lssp_amd_ilu_create for
- * those.  NULL arguments, a kind that is neither ILUK nor ILUT, or nrows !=
+ * tiles), LSSP_AMD_LINE=0, a distributed A (take its lssp_amd_mat_local_block
+ * first), an unsorted row, a missing diagonal or neighbour, any matrix that is
+ * no such box; use lssp_amd_ilu_create for those.  NULL arguments, a kind that is neither ILUK nor ILUT, or nrows !=
  * ncols: LSSP_AMD_EINVAL.  A HIP error part-way: LSSP_AMD_EHIP, everything
  * freed.  Returns when the stream has finished. */
 int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, int level, double tol, int p,
@@ -664,7 +713,8 @@ int lssp_amd_iluk_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind,
  * working row -- a row's L part or U part before the cut to p -- beyond
  * lssp_amd_ilut_capacity() entries (1024).
  * LSSP_AMD_EUNSUPPORTED with *out == NULL, nothing left allocated, A and ctx
- * usable: a distributed A, block-Jacobi, an unsorted row or a repeated column,
+ * usable: a distributed A (take its lssp_amd_mat_local_block first),
+ * block-Jacobi, an unsorted row or a repeated column,
  * a missing diagonal (the reference inserts one first; that path is not
  * reproduced here), a working row beyond the capacity; use lssp_amd_ilu_create
  * for those.  NULL arguments or nrows != ncols: LSSP_AMD_EINVAL.  A bounded
@@ -710,7 +760,9 @@ int lssp_amd_ilut_capacity(void);
  * entry of the factor pattern + 20 B per row): on the packet sweeps
  * lssp_amd_iluk_refactor is eligible on it at once and builds nothing.
  * LSSP_AMD_EUNSUPPORTED from the general route, with *out == NULL, nothing left
- * allocated, A and ctx usable: block-Jacobi, a distributed A, a row whose
+ * allocated, A and ctx usable: block-Jacobi, a distributed A (take its
+ * lssp_amd_mat_local_block first: the rank's slab then gets its line sweeps or
+ * the general route like any matrix), a row whose
  * columns are not strictly ascending inside [0, n), a row without its diagonal
  * (the inserted-diagonal path is not reproduced; lssp_amd_csr_adjust_zero_diag
  * on the device makes such a matrix eligible), a working row beyond
@@ -756,7 +808,8 @@ int lssp_amd_pc_create_dev(lssp_amd_ctx *ctx, const lssp_amd_mat *A, int kind, i
  * refuses it, as it refuses the host-made one.
  * LSSP_AMD_EUNSUPPORTED, with *out == NULL, nothing left allocated, A and ctx
  * usable: bs 9..32 (lssp_amd_bilu_create factors those on the host), a
- * distributed A, a row whose columns are not strictly ascending inside [0, n)
+ * distributed A (take its lssp_amd_mat_local_block first), a row whose columns
+ * are not strictly ascending inside [0, n)
  * (lssp_amd_csr_sort_columns_dev sorts one), a block row without its diagonal
  * block -- lssp_amd_bilu_create gives such a row the identity as its inverse;
  * that path is not reproduced here, at any level --, a working block row beyond

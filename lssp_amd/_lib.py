@@ -108,6 +108,9 @@ SIGNATURES = {
     "lssp_amd_csr_get_block_diag": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "lssp_amd_mat_from_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _pvp]),
     "lssp_amd_mat_update_values": (_ci, [_vp, _vp, _vp, _ci]),
+    "lssp_amd_mat_from_device_dist": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _pvp]),
+    "lssp_amd_mat_local_block": (_ci, [_vp, _vp, _pvp]),
+    "lssp_amd_mat_local_block_refresh": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_ilu_refactor": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_bilu_refactor": (_ci, [_vp, _vp, _vp]),
     "lssp_amd_iluk_refactor": (_ci, [_vp, _vp, _vp]),

@@ -17,7 +17,6 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
-#include <map>
 
 #include "internal.h"
 
@@ -411,71 +410,25 @@ static int agree_status(lssp_amd_ctx *c, int st)
     return LSSP_AMD_OK;
 }
 
-int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal, const int *Ap,
-                             const int *Aj, const double *Ax, lssp_amd_mat **out)
+// The one builder of a distributed handle.  M holds the rank's rows in HBM with
+// GLOBAL columns (Ap, Aj, Ax allocated and filled by the caller, st_in its
+// status so far); the checks, the halo list, the local numbering and the
+// halo-free chunk run are made on the device (convert.hip), the exchange plan
+// through the transport, the codings by build_codings.  Only the halo list, P
+// counts, the send indices and two words per chunk cross to the host.  The
+// guard destroys M on every failing path.
+static int dist_build(lssp_amd_ctx *c, MatGuard &guard, int st_in, lssp_amd_mat **out)
 {
-    if (!c || !out) return LSSP_AMD_EINVAL;  // no context: nothing to agree through
-    const int P = c->nranks;
-    // ---- local checks, then agreed on ----
-    int st = LSSP_AMD_OK;
-    const int blk = n_global > 0 ? (n_global + P - 1) / P : 1;
-    const int my0 = std::min(c->rank * blk, std::max(n_global, 0));
-    const int myn = std::max(0, std::min(blk, n_global - my0));
-    if (!Ap || n_global <= 0 || nlocal < 0 || row0 != my0 || nlocal != myn || Ap[0] != 0)
-        st = LSSP_AMD_EINVAL;  // canonical partition only
-    const int nnz = st == LSSP_AMD_OK ? Ap[nlocal] : 0;
-    if (st == LSSP_AMD_OK && (nnz < 0 || (nnz > 0 && (!Aj || !Ax)))) st = LSSP_AMD_EINVAL;
-    for (int k = 0; st == LSSP_AMD_OK && k < nnz; k++)
-        if (Aj[k] < 0 || Aj[k] >= n_global) st = LSSP_AMD_EINVAL;
-    LSSP_TRY(agree_status(c, st));
-    // halo columns, grouped by owner then ascending
-    std::map<int, int> halo;  // global col -> slot
-    for (int k = 0; k < nnz; k++) {
-        const int g = Aj[k];
-        if (g < row0 || g >= row0 + nlocal) halo[g] = 0;
-    }
-    std::vector<int> hcols;
-    hcols.reserve(halo.size());
-    for (auto &kv : halo) hcols.push_back(kv.first);  // std::map is ordered: owners ascending too
-    for (size_t q = 0; q < hcols.size(); q++) halo[hcols[q]] = (int)q;
-    std::vector<int> lj(nnz);
-    for (int k = 0; k < nnz; k++) {
-        const int g = Aj[k];
-        lj[k] = (g >= row0 && g < row0 + nlocal) ? g - row0 : nlocal + halo[g];
-    }
-    MatGuard guard{new lssp_amd_mat()};
     lssp_amd_mat *M = guard.m;
-    M->ctx = c;
-    M->nrows = nlocal;
-    M->nhalo = (int)hcols.size();
-    M->ncols = nlocal + M->nhalo;
-    M->nnz = nnz;
-    M->n_global = n_global;
-    M->row0 = row0;
-    M->dist = true;
-    {  // the longest run of chunks without a halo-reading row (spmv_halo)
-        const long nch = num_chunks(nlocal);
-        long run0 = 0, best0 = 0, best1 = 0;
-        for (long ch = 0; ch <= nch; ch++) {
-            bool halo_free = ch < nch;
-            for (long i = ch * 256; halo_free && i < std::min<long>((ch + 1) * 256, nlocal); i++)
-                for (int k = Ap[i]; k < Ap[i + 1]; k++)
-                    if (lj[k] >= nlocal) {
-                        halo_free = false;
-                        break;
-                    }
-            if (!halo_free) {
-                if (ch - run0 > best1 - best0) best0 = run0, best1 = ch;
-                run0 = ch + 1;
-            }
-        }
-        M->ich0 = best0;
-        M->ich1 = best1;
-        int mo = 0;  // the halo-free rows' widest reach (the U sweep's tail product, linesweep.hip)
-        for (long i = best0 * 256; i < std::min<long>(best1 * 256, nlocal); i++)
-            for (int k = Ap[i]; k < Ap[i + 1]; k++) mo = std::max(mo, std::abs(lj[k] - (int)i));
-        M->max_off_int = mo;
-    }
+    const int P = c->nranks, n_global = M->n_global, row0 = M->row0, nlocal = M->nrows;
+    const int blk = n_global > 0 ? (n_global + P - 1) / P : 1;
+    int st = st_in;
+    // the structure checks: agreed on before anything indexes with a column
+    if (st == LSSP_AMD_OK) st = dist_check_dev(c, M);
+    LSSP_TRY(agree_status(c, st));
+    // halo columns, grouped by owner then ascending; columns renumbered [owned | halo]
+    std::vector<int> hcols;
+    LSSP_TRY(agree_status(c, dist_localize_dev(c, M, hcols)));
     // receive plan (per owner)
     std::vector<int> need(P, 0);
     for (int g : hcols) need[g / blk]++;
@@ -488,70 +441,68 @@ int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal
         }
         off += need[q];
     }
-    // tell every owner which of its columns we need: counts then index lists
-    DevMem d_cnt_mine, d_cnt_all, d_hcols, d_sendg;
-    st = hipMalloc(&d_cnt_mine.p, sizeof(int) * P) == hipSuccess &&
-                 hipMalloc(&d_cnt_all.p, sizeof(int) * P * P) == hipSuccess &&
-                 hipMemcpy(d_cnt_mine.p, need.data(), sizeof(int) * P, hipMemcpyHostToDevice) == hipSuccess
-             ? LSSP_AMD_OK
-             : LSSP_AMD_ENOMEM;
-    LSSP_TRY(agree_status(c, st));
-    LSSP_TRY(xfer_allgather(c, d_cnt_mine.p, d_cnt_all.p, (long)sizeof(int) * P));
-    std::vector<int> all(P * P);
-    LSSP_HIP(hipMemcpyAsync(all.data(), d_cnt_all.p, sizeof(int) * P * P, hipMemcpyDeviceToHost, c->stream));
-    LSSP_HIP(hipStreamSynchronize(c->stream));
+    // tell every owner which of its columns we need: counts then index lists.
+    // One rank owns every column: no halo, nothing to exchange, and a context
+    // without a communicator builds its handle too
     int nsend = 0;
-    for (int q = 0; q < P; q++) {
-        const int cnt = all[q * P + c->rank];  // what rank q needs from me
-        if (cnt) {
-            M->send_peer.push_back(q);
-            M->send_off.push_back(nsend);
-            M->send_cnt.push_back(cnt);
-            nsend += cnt;
+    std::vector<int> sendg;
+    if (P > 1) {
+        DevMem d_cnt_mine, d_cnt_all, d_hcols, d_sendg;
+        st = hipMalloc(&d_cnt_mine.p, sizeof(int) * P) == hipSuccess &&
+                     hipMalloc(&d_cnt_all.p, sizeof(int) * P * P) == hipSuccess &&
+                     hipMemcpy(d_cnt_mine.p, need.data(), sizeof(int) * P, hipMemcpyHostToDevice) == hipSuccess
+                 ? LSSP_AMD_OK
+                 : LSSP_AMD_ENOMEM;
+        LSSP_TRY(agree_status(c, st));
+        LSSP_TRY(xfer_allgather(c, d_cnt_mine.p, d_cnt_all.p, (long)sizeof(int) * P));
+        std::vector<int> all(P * P);
+        LSSP_HIP(hipMemcpyAsync(all.data(), d_cnt_all.p, sizeof(int) * P * P, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        for (int q = 0; q < P; q++) {
+            const int cnt = all[q * P + c->rank];  // what rank q needs from me
+            if (cnt) {
+                M->send_peer.push_back(q);
+                M->send_off.push_back(nsend);
+                M->send_cnt.push_back(cnt);
+                nsend += cnt;
+            }
         }
+        st = hipMalloc(&d_hcols.p, sizeof(int) * std::max<size_t>(hcols.size(), 1)) == hipSuccess &&
+                     hipMalloc(&d_sendg.p, sizeof(int) * std::max(nsend, 1)) == hipSuccess &&
+                     (hcols.empty() || hipMemcpy(d_hcols.p, hcols.data(), sizeof(int) * hcols.size(),
+                                                 hipMemcpyHostToDevice) == hipSuccess)
+                 ? LSSP_AMD_OK
+                 : LSSP_AMD_ENOMEM;
+        LSSP_TRY(agree_status(c, st));
+        {
+            std::vector<Msg> s, r;  // my halo columns to their owners; the columns peers need from me
+            int *hc = static_cast<int *>(d_hcols.p), *sg = static_cast<int *>(d_sendg.p);
+            for (size_t q = 0; q < M->recv_peer.size(); q++)
+                s.push_back({M->recv_peer[q], hc + M->recv_off[q], (long)sizeof(int) * M->recv_cnt[q]});
+            for (size_t q = 0; q < M->send_peer.size(); q++)
+                r.push_back({M->send_peer[q], sg + M->send_off[q], (long)sizeof(int) * M->send_cnt[q]});
+            LSSP_TRY(xfer_group(c, s, r));
+        }
+        sendg.resize(nsend);
+        if (nsend)
+            LSSP_HIP(hipMemcpyAsync(sendg.data(), d_sendg.p, sizeof(int) * nsend, hipMemcpyDeviceToHost, c->stream));
+        LSSP_HIP(hipStreamSynchronize(c->stream));
+        // a peer asking for a column this rank does not own: every rank learns it
+        st = LSSP_AMD_OK;
+        for (int &g : sendg) {
+            if (g < row0 || g >= row0 + nlocal) st = LSSP_AMD_EINVAL;
+            g -= row0;
+        }
+        LSSP_TRY(agree_status(c, st));
     }
     M->nsend = nsend;
-    st = hipMalloc(&d_hcols.p, sizeof(int) * std::max<size_t>(hcols.size(), 1)) == hipSuccess &&
-                 hipMalloc(&d_sendg.p, sizeof(int) * std::max(nsend, 1)) == hipSuccess &&
-                 (hcols.empty() || hipMemcpy(d_hcols.p, hcols.data(), sizeof(int) * hcols.size(),
-                                             hipMemcpyHostToDevice) == hipSuccess)
-             ? LSSP_AMD_OK
-             : LSSP_AMD_ENOMEM;
-    LSSP_TRY(agree_status(c, st));
-    {
-        std::vector<Msg> s, r;  // my halo columns to their owners; the columns peers need from me
-        int *hc = static_cast<int *>(d_hcols.p), *sg = static_cast<int *>(d_sendg.p);
-        for (size_t q = 0; q < M->recv_peer.size(); q++)
-            s.push_back({M->recv_peer[q], hc + M->recv_off[q], (long)sizeof(int) * M->recv_cnt[q]});
-        for (size_t q = 0; q < M->send_peer.size(); q++)
-            r.push_back({M->send_peer[q], sg + M->send_off[q], (long)sizeof(int) * M->send_cnt[q]});
-        LSSP_TRY(xfer_group(c, s, r));
-    }
-    std::vector<int> sendg(nsend);
-    if (nsend)
-        LSSP_HIP(hipMemcpyAsync(sendg.data(), d_sendg.p, sizeof(int) * nsend, hipMemcpyDeviceToHost, c->stream));
-    LSSP_HIP(hipStreamSynchronize(c->stream));
-    // a peer asking for a column this rank does not own: every rank learns it
-    st = LSSP_AMD_OK;
-    for (int &g : sendg) {
-        if (g < row0 || g >= row0 + nlocal) st = LSSP_AMD_EINVAL;
-        g -= row0;
-    }
-    LSSP_TRY(agree_status(c, st));
-    // the matrix's own buffers (the largest allocations of the upload): a
-    // failure becomes a status that every rank agrees on, and MatGuard frees
-    // whatever was allocated
+    // the pack indices and the send buffer: a failure becomes a status that every
+    // rank agrees on, and the guard frees whatever was allocated
     auto dev_ok = [](hipError_t e) { return e == hipSuccess; };
     const bool ok =
         dev_ok(hipMalloc(&M->d_send_idx, sizeof(int) * std::max(nsend, 1))) &&
         dev_ok(hipMalloc(&M->d_send_buf, sizeof(double) * std::max(nsend, 1))) &&
-        (!nsend || dev_ok(hipMemcpy(M->d_send_idx, sendg.data(), sizeof(int) * nsend, hipMemcpyHostToDevice))) &&
-        dev_ok(hipMalloc(&M->Ap, sizeof(int) * (nlocal + 1))) &&
-        dev_ok(hipMalloc(&M->Aj, sizeof(int) * ((size_t)nnz + 4))) &&  // +4: see upload_csr (capi.cpp)
-        dev_ok(hipMalloc(&M->Ax, sizeof(double) * ((size_t)nnz + 4))) &&
-        dev_ok(hipMemcpy(M->Ap, Ap, sizeof(int) * (nlocal + 1), hipMemcpyHostToDevice)) &&
-        (!nnz || (dev_ok(hipMemcpy(M->Aj, lj.data(), sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice)) &&
-                  dev_ok(hipMemcpy(M->Ax, Ax, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice))));
+        (!nsend || dev_ok(hipMemcpy(M->d_send_idx, sendg.data(), sizeof(int) * nsend, hipMemcpyHostToDevice)));
     if (!ok) (void)hipGetLastError();  // clear the sticky error of a failed allocation
     LSSP_TRY(agree_status(c, ok ? LSSP_AMD_OK : LSSP_AMD_ENOMEM));
     // the SpMV's codings (convert.hip), each layer's status agreed on.  max_off_int
@@ -560,6 +511,83 @@ int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal
     guard.m = nullptr;
     *out = M;
     return LSSP_AMD_OK;
+}
+
+// the half-built handle of the rank's rows: its fields, and the CSR buffers
+// padded as upload_csr (capi.cpp) pads them.  ENOMEM when one cannot be had
+static int dist_alloc(lssp_amd_ctx *c, lssp_amd_mat *M, int n_global, int row0, int nlocal, int nnz)
+{
+    M->ctx = c;
+    M->nrows = M->ncols = nlocal;
+    M->nnz = nnz;
+    M->n_global = n_global;
+    M->row0 = row0;
+    M->dist = true;
+    if (hipMalloc(&M->Ap, sizeof(int) * ((size_t)nlocal + 1)) == hipSuccess &&
+        hipMalloc(&M->Aj, sizeof(int) * ((size_t)nnz + 4)) == hipSuccess &&
+        hipMalloc(&M->Ax, sizeof(double) * ((size_t)nnz + 4)) == hipSuccess)
+        return LSSP_AMD_OK;
+    (void)hipGetLastError();
+    return LSSP_AMD_ENOMEM;
+}
+
+// the canonical partition: rank r holds rows [r blk, r blk + blk) of n_global, blk = ceil(n_global / P)
+static bool canonical_rows(const lssp_amd_ctx *c, int n_global, int row0, int nlocal)
+{
+    const int P = c->nranks;
+    const int blk = n_global > 0 ? (n_global + P - 1) / P : 1;
+    const int my0 = std::min(c->rank * blk, std::max(n_global, 0));
+    const int myn = std::max(0, std::min(blk, n_global - my0));
+    return n_global > 0 && nlocal >= 0 && row0 == my0 && nlocal == myn;
+}
+
+int lssp_amd_mat_upload_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal, const int *Ap,
+                             const int *Aj, const double *Ax, lssp_amd_mat **out)
+{
+    if (!c || !out) return LSSP_AMD_EINVAL;  // no context: nothing to agree through
+    // ---- what the host pointers allow to check, then agreed on ----
+    int st = LSSP_AMD_OK;
+    if (!Ap || !canonical_rows(c, n_global, row0, nlocal) || Ap[0] != 0) st = LSSP_AMD_EINVAL;  // canonical partition only
+    const int nnz = st == LSSP_AMD_OK ? Ap[nlocal] : 0;
+    if (st == LSSP_AMD_OK && (nnz < 0 || (nnz > 0 && (!Aj || !Ax)))) st = LSSP_AMD_EINVAL;
+    LSSP_TRY(agree_status(c, st));
+    (void)hipSetDevice(c->device);
+    // the rows to HBM as they are; the rest is the device builder's
+    MatGuard guard{new lssp_amd_mat()};
+    lssp_amd_mat *M = guard.m;
+    st = dist_alloc(c, M, n_global, row0, nlocal, nnz);
+    if (st == LSSP_AMD_OK) {
+        const bool ok =
+            hipMemcpy(M->Ap, Ap, sizeof(int) * ((size_t)nlocal + 1), hipMemcpyHostToDevice) == hipSuccess &&
+            (!nnz || (hipMemcpy(M->Aj, Aj, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice) == hipSuccess &&
+                      hipMemcpy(M->Ax, Ax, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice) == hipSuccess));
+        if (!ok) (void)hipGetLastError(), st = LSSP_AMD_EHIP;
+    }
+    return dist_build(c, guard, st, out);
+}
+
+int lssp_amd_mat_from_device_dist(lssp_amd_ctx *c, int n_global, int row0, int nlocal, int nnz, const int *dAp,
+                                  const int *dAj, const double *dAx, lssp_amd_mat **out)
+{
+    if (!c || !out) return LSSP_AMD_EINVAL;  // no context: nothing to agree through
+    int st = LSSP_AMD_OK;
+    if (!dAp || !canonical_rows(c, n_global, row0, nlocal) || nnz < 0 || (nnz > 0 && (!dAj || !dAx)))
+        st = LSSP_AMD_EINVAL;
+    LSSP_TRY(agree_status(c, st));
+    (void)hipSetDevice(c->device);
+    MatGuard guard{new lssp_amd_mat()};
+    lssp_amd_mat *M = guard.m;
+    st = dist_alloc(c, M, n_global, row0, nlocal, nnz);
+    if (st == LSSP_AMD_OK) {
+        hipStream_t s = c->stream;
+        const bool ok =
+            hipMemcpyAsync(M->Ap, dAp, sizeof(int) * ((size_t)nlocal + 1), hipMemcpyDeviceToDevice, s) == hipSuccess &&
+            (!nnz || (hipMemcpyAsync(M->Aj, dAj, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToDevice, s) == hipSuccess &&
+                      hipMemcpyAsync(M->Ax, dAx, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, s) ==
+                          hipSuccess));
+        if (!ok) (void)hipGetLastError(), st = LSSP_AMD_EHIP;
+    }
+    return dist_build(c, guard, st, out);
 }
 
 }  // extern "C"

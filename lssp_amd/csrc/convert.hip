@@ -24,7 +24,10 @@
 // (matrix-utils.cxx:217-279, :387-698) on device arrays, and
 // lssp_amd_mat_from_device, which builds the handle lssp_amd_mat_upload
 // (capi.cpp) builds from a CSR in HBM; and the SpMV's codings of every
-// handle (build_codings: offset ids, row codes, value codes).
+// handle (build_codings: offset ids, row codes, value codes).  Also the device
+// half of the distributed builder (dist_check_dev, dist_localize_dev; the
+// collective half is comm.cpp's) and the rank's diagonal block
+// (lssp_amd_mat_local_block, lssp_amd_mat_local_block_refresh).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -478,6 +481,145 @@ __global__ __launch_bounds__(CT) void k_bd_fill(long n, int blk, const int *__re
             Mj[o] = (int)i;
             Mx[o] = 1;
         }
+    }
+}
+
+// ---- a distributed matrix's local numbering (lssp_amd::dist_localize_dev) -------
+// halo entries of row i: the columns outside the rank's rows [row0, row0 + nl)
+__global__ __launch_bounds__(CT) void k_halo_count(long nl, int row0, const int *__restrict__ Ap,
+                                                   const int *__restrict__ Aj, int *__restrict__ cnt)
+{
+    GRID_STRIDE(i, nl)
+    {
+        int c = 0;
+        for (int k = Ap[i]; k < Ap[i + 1]; k++) c += ((unsigned)(Aj[k] - row0) >= (unsigned)nl) ? 1 : 0;
+        cnt[i] = c;
+    }
+}
+
+__global__ __launch_bounds__(CT) void k_halo_fill(long nl, int row0, const int *__restrict__ Ap,
+                                                  const int *__restrict__ Aj, const int *__restrict__ Hp,
+                                                  int *__restrict__ raw)
+{
+    GRID_STRIDE(i, nl)
+    {
+        int o = Hp[i];
+        for (int k = Ap[i]; k < Ap[i + 1]; k++)
+            if ((unsigned)(Aj[k] - row0) >= (unsigned)nl) raw[o++] = Aj[k];
+    }
+}
+
+// the first of every run of equal sorted keys; flag has n + 1 words, the last 0,
+// so its exclusive sum ends with the number of distinct keys
+__global__ __launch_bounds__(CT) void k_first_flag(long n, const unsigned *__restrict__ key, int *__restrict__ flag)
+{
+    GRID_STRIDE(i, n + 1) flag[i] = (i < n && (i == 0 || key[i] != key[i - 1])) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(CT) void k_first_put(long n, const unsigned *__restrict__ key,
+                                                  const int *__restrict__ pos, int *__restrict__ out)
+{
+    GRID_STRIDE(i, n)
+    {
+        if (i == 0 || key[i] != key[i - 1]) out[pos[i]] = (int)key[i];
+    }
+}
+
+// global column -> local: an owned column g - row0, a halo column nl + its rank
+// in the ascending halo list (bisection).  Four entries per thread, 16-byte
+// accesses: Aj is padded to a multiple of four entries (nnz + 4 allocated)
+__global__ __launch_bounds__(CT) void k_localize(long nnz, int row0, int nl, const int *__restrict__ hcols,
+                                                 int nhalo, int *__restrict__ Aj)
+{
+    GRID_STRIDE(q, (nnz + 3) / 4)
+    {
+        int4 v = reinterpret_cast<const int4 *>(Aj)[q];
+        int g[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            if (4 * q + t >= nnz) continue;  // the padding passes through
+            if ((unsigned)(g[t] - row0) < (unsigned)nl) {
+                g[t] -= row0;
+                continue;
+            }
+            int lo = 0, hi = nhalo;
+            while (lo < hi) {
+                int mid = (lo + hi) >> 1;
+                if (hcols[mid] < g[t])
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            g[t] = nl + lo;
+        }
+        reinterpret_cast<int4 *>(Aj)[q] = make_int4(g[0], g[1], g[2], g[3]);
+    }
+}
+
+// per 256-row chunk of the localized matrix: does a row read a halo column, and
+// the rows' widest |col - row| (a workgroup per chunk, a thread per row)
+__global__ __launch_bounds__(CT) void k_chunk_halo(long nch, int nl, const int *__restrict__ Ap,
+                                                   const int *__restrict__ Aj, int *__restrict__ ch_halo,
+                                                   int *__restrict__ ch_off)
+{
+    __shared__ int s_halo, s_off;
+    for (long ch = blockIdx.x; ch < nch; ch += gridDim.x) {
+        if (threadIdx.x == 0) s_halo = 0, s_off = 0;
+        __syncthreads();
+        const long i = ch * CT + threadIdx.x;
+        int halo = 0, mo = 0;
+        if (i < nl)
+            for (int k = Ap[i]; k < Ap[i + 1]; k++) {
+                const int j = Aj[k];
+                halo |= j >= nl ? 1 : 0;
+                const int d = j - (int)i;
+                mo = max(mo, d < 0 ? -d : d);
+            }
+        if (halo) atomicOr(&s_halo, 1);
+        if (mo) atomicMax(&s_off, mo);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            ch_halo[ch] = s_halo;
+            ch_off[ch] = s_off;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- the rank's diagonal block (lssp_amd_mat_local_block) ----------------------
+// entries of row i whose local column is owned (below nl); cnt has nl + 1 words
+__global__ __launch_bounds__(CT) void k_lb_count(long nl, const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                 int *__restrict__ cnt)
+{
+    GRID_STRIDE(i, nl)
+    {
+        int c = 0;
+        for (int k = Ap[i]; k < Ap[i + 1]; k++) c += Aj[k] < (int)nl ? 1 : 0;
+        cnt[i] = c;
+    }
+}
+
+// the block's entries in A's order.  Bj == nullptr: the values alone, into a
+// block whose row pointers are given (the refresh); a row whose owned entries are
+// not exactly Bp's raises err and writes nothing past its slots
+__global__ __launch_bounds__(CT) void k_lb_fill(long nl, const int *__restrict__ Ap, const int *__restrict__ Aj,
+                                                const double *__restrict__ Ax, const int *__restrict__ Bp,
+                                                int *__restrict__ Bj, double *__restrict__ Bx,
+                                                int *__restrict__ err)
+{
+    GRID_STRIDE(i, nl)
+    {
+        int o = Bp[i];
+        const int e = Bp[i + 1];
+        for (int k = Ap[i]; k < Ap[i + 1]; k++)
+            if (Aj[k] < (int)nl) {
+                if (o < e) {
+                    if (Bj) Bj[o] = Aj[k];
+                    Bx[o] = Ax[k];
+                }
+                o++;
+            }
+        if (o != e) atomicOr(err, 1);
     }
 }
 
@@ -1108,10 +1250,96 @@ int lssp_amd::build_codings(lssp_amd_ctx *c, lssp_amd_mat *M, int (*step)(lssp_a
     TRY(done(build_off_ids(c, M, M->nhalo == 0)));
     TRY(done(build_row_codes(c, M)));
     // A distributed matrix is not value-coded and stays on COL_ROW: its
-    // products are split at the halo rows and its values cannot be refreshed,
-    // so the eligibility test would need one more agreement round
+    // products are split at the halo rows, so the eligibility test would need
+    // one more agreement round (and lssp_amd_mat_update_values a collective)
     if (M->dist) return LSSP_AMD_OK;
     return done(build_val_codes(c, M));
+}
+
+// The structure checks of a distributed matrix whose local rows are resident
+// with GLOBAL columns: Ap[0] == 0, Ap non-decreasing, Ap[nrows] == nnz, every
+// column in [0, n_global).  Nothing indexes with a column before this passed.
+int lssp_amd::dist_check_dev(lssp_amd_ctx *c, const lssp_amd_mat *M)
+{
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(err, int, 1);
+    LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    k_check_ptr<<<grid_for((long)M->nrows + 1), CT, 0, s>>>(M->nrows, M->nnz, M->Ap, err);
+    if (M->nnz > 0) k_check_idx<<<grid_for(M->nnz), CT, 0, s>>>(M->nnz, M->Aj, M->n_global, err);
+    LSSP_HIP(hipGetLastError());
+    return checked(s, err);
+}
+
+// The local numbering of a checked distributed matrix, in place: hcols comes
+// back as the halo columns, ascending (= grouped by owner, then ascending: the
+// owners hold contiguous ranges); Aj becomes [owned | halo]; nhalo, ncols, the
+// longest run [ich0, ich1) of halo-free 256-row chunks (the first of equals)
+// and max_off_int over its rows are set.  Local to the rank: no collective.
+// Only the halo list and two words per chunk cross to the host.
+int lssp_amd::dist_localize_dev(lssp_amd_ctx *c, lssp_amd_mat *M, std::vector<int> &hcols)
+{
+    const int nl = M->nrows, nnz = M->nnz, row0 = M->row0;
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    hcols.clear();
+    int nh = 0;
+    if (nl > 0 && nnz > 0) {
+        SCRATCH(cnt, int, (long)nl + 1);
+        SCRATCH(Hp, int, (long)nl + 1);
+        LSSP_HIP(hipMemsetAsync(cnt + nl, 0, sizeof(int), s));
+        k_halo_count<<<grid_for(nl), CT, 0, s>>>(nl, row0, M->Ap, M->Aj, cnt);
+        int nraw = 0;
+        TRY(exclusive_sum(S, cnt, Hp, (long)nl + 1));
+        TRY(fetch(s, Hp + nl, &nraw));
+        if (nraw > 0) {
+            SCRATCH(raw, unsigned, nraw);
+            SCRATCH(srt, unsigned, nraw);
+            SCRATCH(flag, int, (long)nraw + 1);
+            SCRATCH(pos, int, (long)nraw + 1);
+            k_halo_fill<<<grid_for(nl), CT, 0, s>>>(nl, row0, M->Ap, M->Aj, Hp, (int *)raw);
+            TRY(sort_keys(S, (const unsigned *)raw, srt, nraw, bits_for((unsigned)(M->n_global - 1))));
+            k_first_flag<<<grid_for((long)nraw + 1), CT, 0, s>>>(nraw, srt, flag);
+            TRY(exclusive_sum(S, flag, pos, (long)nraw + 1));
+            TRY(fetch(s, pos + nraw, &nh));
+            int *uniq = (int *)raw;  // the unsorted list is done with
+            k_first_put<<<grid_for(nraw), CT, 0, s>>>(nraw, srt, pos, uniq);
+            LSSP_HIP(hipGetLastError());
+            hcols.resize(nh);
+            LSSP_HIP(hipMemcpyAsync(hcols.data(), uniq, sizeof(int) * (size_t)nh, hipMemcpyDeviceToHost, s));
+            k_localize<<<grid_for(((long)nnz + 3) / 4), CT, 0, s>>>(nnz, row0, nl, uniq, nh, M->Aj);
+        } else {
+            k_localize<<<grid_for(((long)nnz + 3) / 4), CT, 0, s>>>(nnz, row0, nl, nullptr, 0, M->Aj);
+        }
+        LSSP_HIP(hipGetLastError());
+    }
+    M->nhalo = nh;
+    M->ncols = nl + nh;
+    // the longest run of chunks without a halo-reading row (spmv_halo), and the
+    // widest reach of its rows (the U sweep's tail product, linesweep.hip)
+    const long nch = num_chunks(nl);
+    std::vector<int> ch_halo((size_t)nch), ch_off((size_t)nch);
+    if (nch > 0) {
+        SCRATCH(d_halo, int, nch);
+        SCRATCH(d_off, int, nch);
+        k_chunk_halo<<<(unsigned)std::min<long>(nch, 16384), CT, 0, s>>>(nch, nl, M->Ap, M->Aj, d_halo, d_off);
+        LSSP_HIP(hipGetLastError());
+        LSSP_HIP(hipMemcpyAsync(ch_halo.data(), d_halo, sizeof(int) * (size_t)nch, hipMemcpyDeviceToHost, s));
+        LSSP_HIP(hipMemcpyAsync(ch_off.data(), d_off, sizeof(int) * (size_t)nch, hipMemcpyDeviceToHost, s));
+    }
+    LSSP_HIP(hipStreamSynchronize(s));
+    long run0 = 0, best0 = 0, best1 = 0;
+    for (long ch = 0; ch <= nch; ch++)
+        if (ch == nch || ch_halo[ch]) {
+            if (ch - run0 > best1 - best0) best0 = run0, best1 = ch;
+            run0 = ch + 1;
+        }
+    M->ich0 = best0;
+    M->ich1 = best1;
+    int mo = 0;
+    for (long ch = best0; ch < best1; ch++) mo = std::max(mo, ch_off[ch]);
+    M->max_off_int = mo;
+    return LSSP_AMD_OK;
 }
 
 extern "C" {
@@ -1528,7 +1756,6 @@ int lssp_amd_mat_from_device(lssp_amd_ctx *c, int nrows, int ncols, int nnz, con
 int lssp_amd_mat_update_values(lssp_amd_ctx *c, lssp_amd_mat *A, const double *dAx, int nnz)
 {
     if (!c || !A || !dAx || nnz != A->nnz) return LSSP_AMD_EINVAL;
-    if (A->dist) return LSSP_AMD_EUNSUPPORTED;
     if (nnz == 0) return LSSP_AMD_OK;
     LSSP_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -1540,8 +1767,58 @@ int lssp_amd_mat_update_values(lssp_amd_ctx *c, lssp_amd_mat *A, const double *d
         LSSP_HIP(hipGetLastError());
     }
     LSSP_HIP(hipStreamSynchronize(s));
-    // the value codes describe the old values: rebuilt for the new ones, or dropped
+    // the value codes describe the old values: rebuilt for the new ones, or
+    // dropped.  A distributed matrix has none (build_codings): local, no collective
+    if (A->dist) return LSSP_AMD_OK;
     return lssp_amd::build_val_codes(c, A);
+}
+
+// The rank's diagonal block of a distributed matrix as a single-rank handle:
+// the entries whose local column is owned, in A's order (per-row counts, a scan,
+// a fill), handed to lssp_amd_mat_from_device, so B is the handle of the
+// host-extracted block in every observable way.  A row left without an entry
+// stays empty.
+int lssp_amd_mat_local_block(lssp_amd_ctx *c, const lssp_amd_mat *A, lssp_amd_mat **B)
+{
+    if (!c || !A || !B || A->nrows <= 0) return LSSP_AMD_EINVAL;
+    LSSP_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    const int nl = A->nrows;
+    SCRATCH(cnt, int, (long)nl + 1);
+    SCRATCH(Bp, int, (long)nl + 1);
+    SCRATCH(err, int, 1);
+    LSSP_HIP(hipMemsetAsync(cnt + nl, 0, sizeof(int), s));
+    LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    k_lb_count<<<grid_for(nl), CT, 0, s>>>(nl, A->Ap, A->Aj, cnt);
+    int bnnz = 0;
+    TRY(sized_rows(S, nl, cnt, Bp, &bnnz));
+    SCRATCH(Bj, int, bnnz);
+    SCRATCH(Bx, double, bnnz);
+    k_lb_fill<<<grid_for(nl), CT, 0, s>>>(nl, A->Ap, A->Aj, A->Ax, Bp, Bj, Bx, err);
+    LSSP_HIP(hipGetLastError());
+    return lssp_amd_mat_from_device(c, nl, nl, bnnz, Bp, Bj, Bx, B);
+}
+
+// B's values again from the values A holds now.  The fill goes to a temporary
+// and checks on the way that A's owned entries per row are B's row lengths, so a
+// mismatch leaves B as it was; the rest is lssp_amd_mat_update_values.
+int lssp_amd_mat_local_block_refresh(lssp_amd_ctx *c, lssp_amd_mat *B, const lssp_amd_mat *A)
+{
+    if (!c || !B || !A) return LSSP_AMD_EINVAL;
+    if (B->dist || B->nhalo > 0 || B->nrows != A->nrows || B->ncols != A->nrows) return LSSP_AMD_EINVAL;
+    LSSP_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    Scratch S(s);
+    SCRATCH(Bx, double, B->nnz);
+    SCRATCH(err, int, 1);
+    LSSP_HIP(hipMemsetAsync(err, 0, sizeof(int), s));
+    if (B->nrows > 0) {
+        k_lb_fill<<<grid_for(B->nrows), CT, 0, s>>>(B->nrows, A->Ap, A->Aj, A->Ax, B->Ap, nullptr, Bx, err);
+        LSSP_HIP(hipGetLastError());
+    }
+    TRY(checked(s, err));
+    return lssp_amd_mat_update_values(c, B, Bx, B->nnz);
 }
 
 }  // extern "C"

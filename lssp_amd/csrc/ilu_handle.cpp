@@ -77,7 +77,12 @@ static FactorView plan_view(const RefactorPlan &p) { return FactorView{p.d_Fp, p
 static int check_create_dev_args(lssp_amd_ctx *c, const lssp_amd_mat *A, bool any_kind, int kind, lssp_amd_ilu **out)
 {
     if (out) *out = nullptr;
-    if (!c || !A || !out || A->nrows <= 0 || A->nrows != A->ncols) return LSSP_AMD_EINVAL;
+    if (!c || !A || !out) return LSSP_AMD_EINVAL;
+    // a distributed A is out of scope, not a bad argument: its column space
+    // [owned | halo] is not square, so it is answered before the shape test
+    // (lssp_amd_mat_local_block makes the rank's square block)
+    if (A->dist || A->nhalo > 0) return LSSP_AMD_EUNSUPPORTED;
+    if (A->nrows <= 0 || A->nrows != A->ncols) return LSSP_AMD_EINVAL;
     if (any_kind && kind != LSSP_AMD_ILUK && kind != LSSP_AMD_ILUT) return LSSP_AMD_EINVAL;
     return LSSP_AMD_OK;
 }

@@ -418,6 +418,12 @@ int build_codings(lssp_amd_ctx *c, lssp_amd_mat *M, int (*step)(lssp_amd_ctx *, 
 // the value-code layer alone, from the resident Ap / Ac / Ax.  It first drops
 // the codes the matrix has (lssp_amd_mat_update_values calls it again)
 int build_val_codes(lssp_amd_ctx *c, lssp_amd_mat *M);
+// a distributed matrix whose local rows are resident with GLOBAL columns
+// (convert.hip): the structure checks, then the local numbering in place with
+// the halo list, the halo-free chunk run and max_off_int.  Both are local to
+// the rank; the caller (comm.cpp) agrees on each status
+int dist_check_dev(lssp_amd_ctx *c, const lssp_amd_mat *M);
+int dist_localize_dev(lssp_amd_ctx *c, lssp_amd_mat *M, std::vector<int> &hcols);
 int launch_spmv(lssp_amd_ctx *c, const lssp_amd_mat *A, int epi, double alpha, const double *x,
                 double beta, const double *y, double *z, int nred, const double *w0,
                 const double *w1, long cb = 0, long ce = -1);  // chunks [cb, ce); ce < 0: all

@@ -233,6 +233,40 @@ class DMat:
         self._adopt_handle(dev, h, int(nnz))
         return self
 
+    @classmethod
+    def from_device_dist(cls, dev: Device, n_global: int, row0: int, nlocal: int, nnz: int, Ap: "DIdx", Aj: "DIdx",
+                         Ax: "DVec"):
+        """The distributed handle of local rows [row0, row0 + nlocal) that already live in HBM with
+        GLOBAL columns (lssp_amd_mat_from_device_dist): equal to DMat(dev, Ap, Aj, Ax, dist=(n_global,
+        row0)) of the same arrays; collective, canonical partition only.  It owns copies, so Ap / Aj /
+        Ax may be freed."""
+        h = ctypes.c_void_p()
+        _ck(dev.L.lssp_amd_mat_from_device_dist(dev.h, n_global, row0, nlocal, nnz, Ap.ptr, Aj.ptr, Ax.ptr,
+                                                ctypes.byref(h)), "mat_from_device_dist")
+        self = cls.__new__(cls)
+        self._adopt_handle(dev, h, int(nnz))
+        return self
+
+    def local_block(self) -> "DMat":
+        """The rank's diagonal block as a single-rank handle (lssp_amd_mat_local_block): the entries
+        whose column this rank owns, in this handle's entry order; equal to DMat(dev, bp, bj, bx) of the
+        block cut out on the host.  What DILU.pc_create_dev / bilu_create_dev take for the rank's
+        block-Jacobi factor."""
+        h = ctypes.c_void_p()
+        _ck(self.dev.L.lssp_amd_mat_local_block(self.dev.h, self.h, ctypes.byref(h)), "mat_local_block")
+        n = ctypes.c_int()
+        _ck(self.dev.L.lssp_amd_mat_info(h, None, None, ctypes.byref(n)), "mat_info")
+        B = type(self).__new__(type(self))
+        B._adopt_handle(self.dev, h, n.value)
+        return B
+
+    def refresh_block(self, A: "DMat"):
+        """On a handle from A.local_block(): its values again from the values A holds now
+        (lssp_amd_mat_local_block_refresh), finished as update_values() finishes.  An A whose owned
+        entries per row differ, or a distributed self, raises LsspError with status 1 and leaves self
+        as it was."""
+        _ck(self.dev.L.lssp_amd_mat_local_block_refresh(self.dev.h, self.h, A.h), "mat_local_block_refresh")
+
     @property
     def nx(self) -> int:
         """length a vector multiplied by this matrix must have (owned + halo)"""
@@ -278,7 +312,8 @@ class DMat:
     def update_values(self, ax: DVec):
         """New values (a device vector of nnz entries, in the handle's entry order) on the
         same pattern: lssp_amd_mat_update_values.  Every layout is kept; the value codes
-        (valcodes) are rebuilt for the new values, or dropped."""
+        (valcodes) are rebuilt for the new values, or dropped.  On a distributed handle the call is
+        local to the rank (no collective) and there are no value codes to rebuild."""
         _ck(self.dev.L.lssp_amd_mat_update_values(self.dev.h, self.h, ax.ptr, ax.n), "mat_update_values")
 
     def close(self):
